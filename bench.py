@@ -15,13 +15,18 @@ over the resident shard: prepass (unit split, avg_qspan sums) + chain DP (f/p/v)
 new_seed[], all HIP kernels, results left in HBM.  Reads are independent, so there is no collective
 on the data path; torch.distributed (RCCL) only provides the barrier and the max-over-ranks time.
 
-One JSON line on rank 0: metric/value/unit as BASELINE.json names them, plus
+One JSON line on rank 0: metric/value/unit as BASELINE.json names them, ms_per_step (one timed step), plus
   roofline     -- the chain-DP kernel against the HBM roofline: 24 algorithmic bytes per anchor
                   (16 B mm128_t read + 4 B f + 4 B p written) over its average launch
                   duration, measured with HIP events on the kernel's own stream.
-  cpu_baseline -- the reference's mm_chain_dp_fpga (oracle/_ref, compiled from /root/reference in the
-                  build container) or, if that file is absent, the oracle's port of it, timed on all
-                  host cores over a bounded sample of the same batch (N=1 only).
+A plain run does only that: set up, warm up, time --steps steps, print the line.  --full adds the side
+measurements (N=1 only), each of which takes runs of its own:
+  cpu_baseline -- the reference's mm_chain_dp_fpga (oracle/_ref, compiled from the reference's sources
+                  by `make -C oracle ref`) or, if that file is absent, the oracle's port of it, timed on
+                  all host cores over a bounded sample of the same batch.
+  end_to_end, end_to_end_pipelined, backtrack, device_copy_GBps, pair_evals_per_anchor, other_configs,
+  map_batch, packet_abi -- see measure_extras and the functions it names.
+--dump-outputs DIR writes what the last timed step computed on rank 0 (see dump_outputs) as .npy files.
 """
 import argparse
 import json
@@ -53,8 +58,14 @@ def main():
     ap.add_argument("--preset", default="ava-ont", help="generator + DP preset (ava-ont, map-ont, skew, dense)")
     ap.add_argument("--ring", type=int, default=0, help="LDS ring capacity override (128/256/512)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only to rehearse several ranks on one GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed side measurements (end-to-end rate, copy bandwidth, pair evaluations)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements beside the headline (CPU baseline, end-to-end and packet rates, other configs, ...); "
+                         "off: only the timed steps and the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0: f/p/v and new_seed[] of a seeded sample of reads, "
+                         "new_seed[] counts of every read) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed side measurements (end-to-end rate, copy bandwidth, pair evaluations)")
     ap.add_argument("--cpu-sample-anchors", type=int, default=40_000_000)
     ap.add_argument("--cpu-threads", type=int, default=16, help="host threads of the CPU baseline (16 = one GPU's share of the box)")
     ap.add_argument("--host-threads", type=int, default=16, help="host threads of the synthetic generator")
@@ -125,6 +136,8 @@ def main():
     dev.set_profiling(False)
     stats = dev.stats()
     handed_over = {"to_one_unit_per_wave_kernel": dev.leftover_units(), "to_dense_kernel": dev.deep_units()}   # this rank's last timed step
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, chaindp, dev, par, off)         # before the side measurements reuse the context
 
     # max over ranks of the timed region; sum of anchors
     elapsed_max, total_all = shard.reduce_job(elapsed, total, dist if world > 1 else None,
@@ -133,7 +146,7 @@ def main():
         dist.barrier()
 
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras:      # side measurements only in the single-GPU run, on one GPU's share of the job
+    if args.full and rank == 0 and world == 1 and not args.no_extras:      # side measurements only in the single-GPU run, on one GPU's share of the job
         ns = min(n_reads, READS_PER_GPU)
         sub_off = np.ascontiguousarray(off[:ns + 1])
         sub_a = anchors[:int(sub_off[-1])]
@@ -203,7 +216,7 @@ def main():
             out["roofline"]["kernel_source_sha16_now"] = kernel_source_sha16()
         if "device_copy_GBps" in extras:
             out["roofline"]["frac_of_measured_copy_bw"] = achieved / extras["device_copy_GBps"]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(par, off, anchors, args.cpu_sample_anchors, args.cpu_threads)
             # no published number exists for this metric, so vs_baseline stays null; the measured
             # ratios to the host's own CPU rate are reported under their own names
@@ -216,6 +229,49 @@ def main():
     dev.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE_ANCHORS = 600_000   # anchors of the sampled reads: (3 + 6) float64 columns each, ~43 MB at most
+
+
+def dump_outputs(out_dir, chaindp, dev, par, off):
+    """What a caller of the timed step receives from the resident batch after its last step, as float64 .npy files (every value
+    is an integer that float64 holds exactly; the 64-bit x / y of new_seed[] are split into 32-bit halves):
+      seeds_per_read  new_seed[] records of every read (new_i, chain.c:286-317)
+      sample_reads    the reads sampled: a fixed permutation of the shard (seed SEED), taken while they hold <= DUMP_SAMPLE_ANCHORS
+      f, p, v         mm_chain_dp_fpga's arrays (chain.c:246-284) of the sampled reads, one read after the other
+      new_seed        their new_seed[] records, one row each: x >> 32, x & 0xffffffff, y >> 32, y & 0xffffffff, p, f
+    f/p/v come from chaindp_download (which also writes the singletons' entries the step leaves to it); new_seed[] from the
+    compaction of the same resident results (chaindp_compact_offsets runs it once more and returns the offsets)."""
+    import ctypes as C
+    os.makedirs(out_dir, exist_ok=True)
+    n_reads = len(off) - 1
+    lens = np.diff(off)
+    perm = np.random.default_rng(SEED).permutation(n_reads)
+    take = np.sort(perm[np.cumsum(lens[perm]) <= DUMP_SAMPLE_ANCHORS])
+    soff = np.zeros(n_reads + 1, np.int64)
+    dev._check(dev._lib.chaindp_compact_offsets(dev._ctx, C.byref(par), soff.ctypes.data))
+    seeds = np.zeros(max(int((soff[take + 1] - soff[take]).sum()), 1), chaindp.SEED_DTYPE)
+    k = 0
+    for r in take:
+        n = int(soff[r + 1] - soff[r])
+        dev._check(dev._lib.chaindp_download_seeds(dev._ctx, int(soff[r]), n, seeds[k:].ctypes.data))
+        k += n
+    dev.sync()
+    seeds = seeds[:k]
+    f, p, v = dev.download()
+    idx = np.concatenate([np.arange(off[r], off[r + 1]) for r in take]) if len(take) else np.zeros(0, np.int64)
+    lo = np.uint64(0xffffffff)
+    arrays = {
+        "seeds_per_read": np.diff(soff),
+        "sample_reads": take,
+        "f": f[idx], "p": p[idx], "v": v[idx],
+        "new_seed": np.stack([c.astype(np.float64) for c in (seeds["x"] >> np.uint64(32), seeds["x"] & lo, seeds["y"] >> np.uint64(32),
+                                                             seeds["y"] & lo, seeds["p"], seeds["f"])], 1),
+    }
+    del f, p, v
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float64))
 
 
 def cpu_reference_bounded(par, off, a, threads, budget_s=2.5):

@@ -3,6 +3,8 @@ built, oracle/_ref/*.so (the unmodified reference).  CHECKER ONLY: imported by
 tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg, never by the
 product package."""
 import ctypes as C
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -67,6 +69,51 @@ def oracle():
 
 def have_ref():
     return os.path.exists(REF_SO) and os.path.exists(CAP_SO)
+
+
+REF_DIGESTS = os.path.join(ROOT, "tests", "golden", "ref_digests.json")
+
+
+class RefRecord:
+    """What the unmodified reference returned for one test case, kept as a SHA-256 over the values (tests/golden/ref_digests.json,
+    written by tests/golden/make_ref_digests.py where oracle/_ref is built), so that the comparison holds where it is not.
+    A test feeds the oracle's results to ours() and, where oracle/_ref is built, the reference's results for the same inputs to
+    theirs(); check() compares ours with the live reference's digest and that with the recorded one, or, where the reference
+    is not built, ours with the recorded one."""
+
+    def __init__(self, key):
+        self.key = key
+        self._ours, self._theirs = hashlib.sha256(), hashlib.sha256()
+
+    @staticmethod
+    def _feed(h, arrays):
+        for a in arrays:
+            a = np.ascontiguousarray(a)
+            if a.dtype.names is None:                 # integers by value (int32 / uint64 alike); records by their bytes
+                a = a.astype("<u8").ravel()
+            h.update(np.int64(a.size).tobytes())
+            h.update(a.tobytes())
+
+    def ours(self, *arrays):
+        self._feed(self._ours, arrays)
+
+    def theirs(self, *arrays):
+        self._feed(self._theirs, arrays)
+
+    def check(self):
+        rec = json.load(open(REF_DIGESTS)) if os.path.exists(REF_DIGESTS) else {}
+        if not have_ref():
+            assert self.key in rec, f"no recorded reference result for {self.key} (tests/golden/make_ref_digests.py)"
+            assert self._ours.hexdigest() == rec[self.key], self.key
+            return
+        theirs = self._theirs.hexdigest()
+        assert self._ours.hexdigest() == theirs, self.key
+        if os.environ.get("CHAINDP_RECORD_REF_DIGESTS") == "1":
+            rec[self.key] = theirs
+            with open(REF_DIGESTS, "w") as fh:
+                json.dump(dict(sorted(rec.items())), fh, indent=0)
+                fh.write("\n")
+        assert rec.get(self.key) == theirs, f"the recorded reference result for {self.key} differs from the reference's"
 
 
 def ref_cap():

@@ -13,7 +13,6 @@ from minimap2_chaindp_amd import params as P
 
 SEEDS = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "seeds", "*.npz")))
 REGS = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "regs", "*.npz")))
-needs_ref = pytest.mark.skipif(not ol.have_ref(), reason="oracle/_ref not built")
 
 
 def chains_of(par, a, min_cnt):
@@ -32,31 +31,37 @@ def fixture_reads(path):
         yield par, pv[7], int(g["qlen"][r]), a, mp
 
 
-@needs_ref
 @pytest.mark.parametrize("path", SEEDS, ids=[os.path.basename(p)[:-4] for p in SEEDS])
 def test_gen_regs_and_est_err_match_reference_on_fixtures(path):
     n_hits = n_div = 0
+    rec = ol.RefRecord(f"gen_regs_and_est_err/{os.path.basename(path)[:-4]}")
     for r, (par, min_cnt, qlen, a, mp) in enumerate(fixture_reads(path)):
         if not len(a):
             continue
         u, b = chains_of(par, a, min_cnt)
         for hash_ in (0, 0x9e3779b9 ^ r):
             regs = ol.oracle_gen_regs(hash_, qlen, u, b)
-            exp = ol.ref_gen_regs(hash_, qlen, u, b)
-            assert regs.tobytes() == exp.tobytes(), (r, hash_)
+            rec.ours(regs)
+            if ol.have_ref():
+                exp = ol.ref_gen_regs(hash_, qlen, u, b)
+                assert regs.tobytes() == exp.tobytes(), (r, hash_)
+                rec.theirs(exp)
         n_hits += len(regs)
         if len(regs) and len(mp):
             ref_len = (np.arange(int(regs["rid"].max()) + 1, dtype=np.int64) * 37 % 5000 + regs["re"].max() - 2000).astype(np.int32)
             got, n_match, n_tot = ol.oracle_est_err(ref_len, qlen, regs, b, mp)
-            exp = ol.ref_est_err(ref_len, qlen, regs, b, mp)
-            assert got.tobytes() == exp.tobytes(), (r, "div")
+            rec.ours(got)
+            if ol.have_ref():
+                exp = ol.ref_est_err(ref_len, qlen, regs, b, mp)
+                assert got.tobytes() == exp.tobytes(), (r, "div")
+                rec.theirs(exp)
             assert (n_match[got["div"] >= 0] >= 1).all()
             n_div += int((got["div"] >= 0).sum())
+    rec.check()
     if os.path.basename(path) != "mt_human_self_avaont.npz":      # a genome against itself under ava-ont's NO_DIAG: no chain survives
         assert n_hits > 0 and n_div > 0
 
 
-@needs_ref
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_gen_regs_with_many_chains_and_equal_keys(seed):
     """Hundreds of chains in one read (beyond the 64-element insertion sort of radix_sort_128x) and chains whose keys
@@ -79,10 +84,15 @@ def test_gen_regs_with_many_chains_and_equal_keys(seed):
     k1 = int(u[0] & np.uint64(0xffffffff))
     b[k1] = b[0]
     u[1] = (u[0] >> np.uint64(32) << np.uint64(32)) | (u[1] & np.uint64(0xffffffff))
+    rec = ol.RefRecord(f"gen_regs_with_many_chains_and_equal_keys/{seed}")
     for hash_ in (0, 12345):
         regs = ol.oracle_gen_regs(hash_, 40000, u, b)
-        exp = ol.ref_gen_regs(hash_, 40000, u, b)
-        assert regs.tobytes() == exp.tobytes()
+        rec.ours(regs)
+        if ol.have_ref():
+            exp = ol.ref_gen_regs(hash_, 40000, u, b)
+            assert regs.tobytes() == exp.tobytes()
+            rec.theirs(exp)
+    rec.check()
     assert (np.diff(regs["score"]) <= 0).all()
 
 
