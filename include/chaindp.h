@@ -195,6 +195,66 @@ int chaindp_map_batch(chaindp_ctx_t *ctx, const chaindp_index_t *idx, int flag, 
                       int64_t n_reads, const int64_t *mini_off, const chaindp_anchor_t *mini, const uint32_t *bid, const int32_t *qlen,
                       const uint32_t *hash, int64_t *regs_off, chaindp_reg_t *regs, int64_t regs_cap, int32_t *rep_len, int64_t *n_anchors);
 
+/* ---- the rest of a read's path without alignment: chain_post and mm_set_mapq (map.c:870-877, n_segs == 1) -----------------------
+ * What the reference does with a read's hits after mm_gen_regs when MM_F_CIGAR is unset (align_regs returns its input, map.c:251):
+ *   chain_post (map.c:238-247)   mm_set_parent, mm_select_sub (+ mm_sync_regs / mm_set_sam_pri when it drops hits), mm_join_long
+ *                                (+ mm_squeeze_a, the MM_SEED_LONG_JOIN bit, mm_filter_regs, mm_sync_regs)
+ *   mm_est_err (map.c:872)       unless is_sr
+ *   mm_set_mapq (map.c:876)      unless flag & MM_F_CIGAR (then the call stops after mm_est_err and the caller aligns)
+ * mm_reg1_t::p is NULL throughout, so only the reference's r->p == NULL branches apply.  chaindp_post_opt_t holds the mm_mapopt_t
+ * fields these steps read, each next to the reference line that reads it. */
+#define CHAINDP_F_CIGAR      0x004      /* minimap.h:10 */
+#define CHAINDP_F_SPLICE     0x080      /* minimap.h:15 */
+#define CHAINDP_F_NO_LJOIN   0x400      /* minimap.h:18 */
+#define CHAINDP_F_SR         0x1000     /* minimap.h:20 */
+#define CHAINDP_F_ALL_CHAINS 0x800000   /* minimap.h:31 */
+typedef struct {
+	int32_t flag;               /* opt->flag: MM_F_ALL_CHAINS (map.c:240), MM_F_SPLICE|MM_F_SR|MM_F_NO_LJOIN (map.c:244), MM_F_CIGAR (map.c:251) */
+	float mask_level;           /* opt->mask_level, mm_set_parent (map.c:241, hit.c:151) */
+	float pri_ratio;            /* opt->pri_ratio, mm_select_sub (map.c:242, hit.c:232,237) */
+	int32_t best_n;             /* opt->best_n, mm_select_sub (hit.c:237) */
+	int32_t min_diff;           /* mi->k * 2, mm_select_sub (map.c:242, hit.c:237) */
+	int32_t sub_diff;           /* opt->a * 2 + opt->b, mm_set_parent (map.c:241; read only where r->p != NULL, hit.c:156) */
+	int32_t max_join_long;      /* opt->max_join_long, mm_join_long (hit.c:314-315) */
+	int32_t max_join_short;     /* opt->max_join_short, mm_join_long (hit.c:314) */
+	int32_t min_join_flank_sc;  /* opt->min_join_flank_sc, mm_join_long (hit.c:315) */
+	int32_t min_cnt;            /* opt->min_cnt, mm_filter_regs (hit.c:255) */
+	int32_t min_chain_score;    /* opt->min_chain_score, mm_set_mapq (map.c:876, hit.c:457) */
+	int32_t match_sc;           /* opt->a, mm_set_mapq (map.c:876; read only where r->p != NULL, hit.c:461,464) */
+	int32_t is_sr;              /* context->is_sr: mm_est_err skipped (map.c:872), mm_set_mapq's is_sr (hit.c:462) */
+} chaindp_post_opt_t;
+
+/* chain_post + mm_est_err + mm_set_mapq for every read of the batch, on the hits the last chaindp_gen_regs left in HBM.
+ *   qlen[n_reads], rep_len[n_reads] and mini_pos_off / mini_pos (as in chaindp_est_err) may be NULL: the ones already resident
+ *   (qlen from chaindp_gen_regs, rep_len and mini_pos from chaindp_collect_seeds).  ref_len[rid] = mi->seq[rid].len.
+ *   regs_off[n_reads + 1] receives the CSR offsets of every read's final hits, regs the records (room for regs_cap of them:
+ *   CHAINDP_ERR_CAPACITY, with regs_off filled in, if there are more).
+ *   a_off[n_reads + 1] / a (both optional): each read's chain anchors as chain_post left them (squeezed by mm_join_long, join bits
+ *   set), at the offsets of chaindp_backtrack's b_off; `as` of the returned hits points into them.  a needs b_off[n_reads] entries.
+ * The results go to buffers of the call's own: what chaindp_backtrack and chaindp_gen_regs left stays as it was.  Refused with
+ * CHAINDP_ERR_ARG without a chaindp_gen_regs on this batch, after a chaindp_est_err (its upload replaces the resident hits), and for a
+ * batch with a read of n_segs > 1; CHAINDP_ERR_CAPACITY also for a logf argument (score, n_sub + 1) above 2^24.  Records are
+ * bit-identical to the reference's except div (the device's logf, as chaindp_est_err). */
+int chaindp_chain_post(chaindp_ctx_t *ctx, const chaindp_post_opt_t *opt, const int32_t *qlen, const int32_t *rep_len,
+                       const int32_t *ref_len, int32_t n_ref, const int64_t *mini_pos_off, const uint64_t *mini_pos,
+                       int64_t *regs_off, chaindp_reg_t *regs, int64_t regs_cap, int64_t *a_off, chaindp_anchor_t *a);
+
+/* chaindp_map_batch followed by chaindp_chain_post in one call: minimizers in, the reference's final hits of a non-CIGAR single-segment
+ * run out (read_result_handle after mm_set_mapq, map.c:837-877), with nothing but regs_off and regs coming back over PCIe.  Arguments
+ * as chaindp_map_batch's plus opt, ref_len, n_ref; rep_len (may be NULL) and n_anchors (may be NULL) are by-products. */
+int chaindp_map_reads(chaindp_ctx_t *ctx, const chaindp_index_t *idx, int flag, int max_occ, const chaindp_params_t *par, int min_cnt,
+                      const chaindp_post_opt_t *opt, int64_t n_reads, const int64_t *mini_off, const chaindp_anchor_t *mini, const uint32_t *bid,
+                      const int32_t *qlen, const uint32_t *hash, const int32_t *ref_len, int32_t n_ref, int64_t *regs_off, chaindp_reg_t *regs,
+                      int64_t regs_cap, int32_t *rep_len, int64_t *n_anchors);
+
+/* Exists for tests: the device's logf of the integers 1..kmax (kmax <= 2^24) -- (float)log((double)k) patched where the host's logf
+ * rounds differently -- and mm_set_mapq's n_sub term of them ((int)(4.343f * logf(k) + .499f), hit.c:474) compared with the host's;
+ * returns the number of integers where either differs (>= 0) or an error code. */
+int64_t chaindp_post_logf_selftest(chaindp_ctx_t *ctx, int32_t kmax);
+/* Exists for tests, needs no GPU: the host's patch list (the integers k in [1, 2^24] where logf((float)k) differs from
+ * (float)log((double)k), ascending, and the host's logf there).  Returns the list's length; copies up to cap entries. */
+int64_t chaindp_post_logf_patches(uint32_t *k, float *v, int64_t cap);
+
 /* Pinned host memory (hipHostMalloc) for callers that want DMA-able staging buffers. */
 void *chaindp_host_alloc(size_t bytes);
 void chaindp_host_free(void *p);

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .params import ChainParams
+from .params import ChainParams, PostOpt
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CHAINDP_LIB: an alternative build of the same library (A/B timing of kernel variants on one box, tools/ab.sh)
@@ -29,6 +29,7 @@ ABI_SYMBOLS = (
     "chaindp_gen_regs", "chaindp_est_err",
     "chaindp_pipe_create", "chaindp_pipe_destroy", "chaindp_pipe_submit", "chaindp_pipe_wait", "chaindp_pipe_release",
     "chaindp_pipe_last_error", "chaindp_map_batch",
+    "chaindp_chain_post", "chaindp_map_reads", "chaindp_post_logf_selftest", "chaindp_post_logf_patches",
 )
 
 # chaindp_reg_t == mm_reg1_t (minimap.h:100-115), 80 bytes; `bits` is the bit-field word (rev = bit 10)
@@ -93,6 +94,13 @@ def lib():
         L.chaindp_device_count.argtypes = []
         L.chaindp_download_anchors.argtypes = [vp, vp]
         L.chaindp_map_batch.argtypes = [vp, vp, i32, i32, P, i32, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]
+        PO = C.POINTER(PostOpt)
+        L.chaindp_chain_post.argtypes = [vp, PO, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp]
+        L.chaindp_map_reads.argtypes = [vp, vp, i32, i32, P, i32, PO, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, i64, vp, vp]
+        L.chaindp_post_logf_selftest.restype = i64
+        L.chaindp_post_logf_selftest.argtypes = [vp, i32]
+        L.chaindp_post_logf_patches.restype = i64
+        L.chaindp_post_logf_patches.argtypes = [vp, vp, i64]
         L.chaindp_pipe_create.restype = vp
         L.chaindp_pipe_create.argtypes = [i32, i32, i64, i64]
         L.chaindp_pipe_destroy.restype = None
@@ -104,6 +112,16 @@ def lib():
         L.chaindp_pipe_last_error.argtypes = [vp]
         _lib = L
     return _lib
+
+
+def post_logf_patches():
+    """The host's logf patch list (needs no GPU): (k uint32[n], logf(k) float32[n]) for the integers k in [1, 2^24] where the host's
+    logf differs from the correctly rounded (float)log((double)k)."""
+    L = lib()
+    n = int(L.chaindp_post_logf_patches(None, None, 0))
+    k, v = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.float32)
+    L.chaindp_post_logf_patches(_ptr(k), _ptr(v), n)
+    return k[:n], v[:n]
 
 
 def device_count():
@@ -288,6 +306,57 @@ class Device:
             self._check(rc)
         self._n_reads, self._total = n_reads, int(na.value)
         return roff, regs[:int(roff[-1])], rep[:n_reads], int(na.value)
+
+    # -- chain_post + mm_est_err + mm_set_mapq (map.c:870-877, one segment, no alignment), after gen_regs() / map_batch()
+    def chain_post(self, opt, ref_len, qlen=None, rep_len=None, mini_pos_off=None, mini_pos=None, regs_cap=None, want_anchors=False):
+        """The final hits of every read (chaindp_chain_post) from the hits gen_regs() left on the device: (regs_off int64[n_reads+1],
+        regs REG_DTYPE[...]) and, with want_anchors, (a_off int64[n_reads+1], a uint64[...,2]): the anchors as chain_post left them.
+        qlen / rep_len / mini_pos None: the ones already on the device.  regs_cap None: room for every input hit (never fewer)."""
+        n_reads = self._n_reads
+        ref_len = np.ascontiguousarray(ref_len, np.int32)
+        ql = None if qlen is None else np.ascontiguousarray(qlen, np.int32)
+        rl = None if rep_len is None else np.ascontiguousarray(rep_len, np.int32)
+        mpo = None if mini_pos_off is None else np.ascontiguousarray(mini_pos_off, np.int64)
+        mp = None if mini_pos is None else np.ascontiguousarray(mini_pos, np.uint64)
+        cap = int(regs_cap) if regs_cap is not None else max(self._total, 1)
+        roff = np.zeros(n_reads + 1, np.int64)
+        regs = np.zeros(max(cap, 1), REG_DTYPE)
+        aoff = np.zeros(n_reads + 1, np.int64) if want_anchors else None
+        a = np.zeros((max(self._total, 1), 2), np.uint64) if want_anchors else None
+        self._check(self._lib.chaindp_chain_post(self._ctx, C.byref(opt), _ptr(ql), _ptr(rl), _ptr(ref_len) if len(ref_len) else None, len(ref_len),
+                                                 _ptr(mpo), None if mp is None or not len(mp) else _ptr(mp), _ptr(roff), _ptr(regs), cap,
+                                                 _ptr(aoff), _ptr(a)))
+        regs = regs[:int(roff[-1])]
+        return (roff, regs, aoff, a[:int(aoff[-1])]) if want_anchors else (roff, regs)
+
+    def map_reads(self, index, flag, max_occ, par, min_cnt, opt, mini_off, mini, bid, qlen, hash_, ref_len, regs_cap=None):
+        """Minimizers in, final hits out (chaindp_map_reads): (regs_off int64[n_reads+1], regs REG_DTYPE[...], rep_len int32[n_reads],
+        n_anchors).  regs_cap None: a guess from the minimizer count, retried with the exact count if the hits need more."""
+        mini_off = np.ascontiguousarray(mini_off, np.int64)
+        n_reads = len(mini_off) - 1
+        mini = np.ascontiguousarray(mini, np.uint64).reshape(-1, 2)
+        bid = np.ascontiguousarray(bid, np.uint32); qlen = np.ascontiguousarray(qlen, np.int32); hash_ = np.ascontiguousarray(hash_, np.uint32)
+        ref_len = np.ascontiguousarray(ref_len, np.int32)
+        cap = int(regs_cap) if regs_cap is not None else max(len(mini) // 4, 1024)
+        roff = np.zeros(n_reads + 1, np.int64); rep = np.zeros(max(n_reads, 1), np.int32)
+        regs = np.zeros(max(cap, 1), REG_DTYPE)
+        na = C.c_int64(0)
+        rc = self._lib.chaindp_map_reads(self._ctx, index, int(flag), int(max_occ), C.byref(par), int(min_cnt), C.byref(opt), n_reads, _ptr(mini_off),
+                                         _ptr(mini), _ptr(bid), _ptr(qlen), _ptr(hash_), _ptr(ref_len) if len(ref_len) else None, len(ref_len),
+                                         _ptr(roff), _ptr(regs), cap, _ptr(rep), C.byref(na))
+        self._n_reads, self._total = n_reads, int(na.value)
+        if rc == -2 and int(roff[-1]) > cap:                                   # more hits than guessed: run the post steps again with room for them
+            roff, regs = self.chain_post(opt, ref_len, regs_cap=int(roff[-1]))
+        else:
+            self._check(rc)
+        return roff, regs[:int(roff[-1])], rep[:n_reads], int(na.value)
+
+    def post_logf_selftest(self, kmax=1 << 24):
+        """Mismatches of the device's logf of the integers 1..kmax against the host's (0 expected)."""
+        n = self._lib.chaindp_post_logf_selftest(self._ctx, int(kmax))
+        if n < 0:
+            self._check(int(n))
+        return int(n)
 
     # -- device-pointer path (torch tensors or any other HBM allocation)
     def run_device(self, par, n_reads, total, d_off, d_a, d_n_segs, d_f, d_p, d_v, stream=0):

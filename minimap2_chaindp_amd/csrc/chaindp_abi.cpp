@@ -7,6 +7,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <math.h>
+#include <mutex>
 #include <string>
 #include <vector>
 #include "../../include/chaindp.h"
@@ -86,6 +88,15 @@ struct chaindp_ctx {
 	unsigned long long *d_sum_k = nullptr;
 	int64_t bot_n_reads = -1, bot_n_chains = 0, bot_n_b = 0;   // what the last chaindp_backtrack left resident (-1: nothing of this batch)
 	bool mp_resident = false;                                  // this batch's mini_pos are on the device (it came from chaindp_collect_seeds)
+	bool regs_resident = false;      // d_regs / d_rqlen hold what chaindp_gen_regs made of the resident chains (chaindp_est_err's upload clears it)
+	// chain_post + mm_set_mapq (allocated on first use, grown with the batch; freed with bot_allocs)
+	void *d_post_stage = nullptr, *d_post_out = nullptr, *d_post_sq = nullptr, *d_post_scratch = nullptr;
+	size_t post_stage_cap = 0, post_out_cap = 0, post_sq_cap = 0, post_scratch_cap = 0;
+	unsigned long long *d_post_off = nullptr, *d_post_tile = nullptr;
+	int32_t *d_post_qlen = nullptr, *d_post_rep = nullptr, *d_post_err = nullptr;
+	uint32_t *d_logf_k = nullptr;
+	float *d_logf_v = nullptr;
+	int n_logf = -1;
 	// profiling
 	bool prof = false;
 	std::vector<EventSet> pending;
@@ -472,6 +483,7 @@ extern "C" int chaindp_backtrack(chaindp_ctx_t *ctx, const chaindp_params_t *par
 	if (rc) return rc;
 	if (!ctx->ran || !ctx->d_seeds) { ctx->err = "chaindp_backtrack needs a completed run and compaction"; return CHAINDP_ERR_ARG; }
 	if (!chains_off || !b_off) { ctx->err = "NULL output"; return CHAINDP_ERR_ARG; }
+	ctx->regs_resident = false;
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	// the record count of the last compaction (it may have been launched asynchronously by chaindp_run_full)
 	unsigned long long n_seeds = 0;
@@ -550,14 +562,16 @@ static int regs_per_read_buffers(chaindp_ctx *ctx)
 	return CHAINDP_OK;
 }
 
-extern "C" int chaindp_gen_regs(chaindp_ctx_t *ctx, const uint32_t *hash, const int32_t *qlen, chaindp_reg_t *regs)
+// download = false: the hits stay in HBM only (chaindp_map_reads)
+static int gen_regs_impl(chaindp_ctx *ctx, const uint32_t *hash, const int32_t *qlen, chaindp_reg_t *regs, bool download)
 {
 	if (!ctx) return CHAINDP_ERR_ARG;
 	if (ctx->bot_n_reads < 0 || ctx->bot_n_reads != ctx->n_reads || !ctx->bot.has) { ctx->err = "chaindp_gen_regs needs the chains of a chaindp_backtrack on this batch"; return CHAINDP_ERR_ARG; }
 	const int64_t R = ctx->bot_n_reads, n_c = ctx->bot_n_chains;
 	if (R > 0 && (!hash || !qlen)) { ctx->err = "NULL hash or qlen"; return CHAINDP_ERR_ARG; }
-	if (n_c > 0 && !regs) { ctx->err = "NULL output"; return CHAINDP_ERR_ARG; }
-	if (R == 0 || n_c == 0) return CHAINDP_OK;
+	if (download && n_c > 0 && !regs) { ctx->err = "NULL output"; return CHAINDP_ERR_ARG; }
+	ctx->regs_resident = false;
+	if (R == 0 || n_c == 0) { ctx->regs_resident = true; return CHAINDP_OK; }
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	int rc = regs_per_read_buffers(ctx);
 	if (rc) return rc;
@@ -568,9 +582,15 @@ extern "C" int chaindp_gen_regs(chaindp_ctx_t *ctx, const uint32_t *hash, const 
 	// sort keys go to the backtrack's 16-byte scratch (free once the chains are out), range stacks to its stack area
 	HIP_TRY(ctx, chaindp::launch_gen_regs(st, R, ctx->bot.chains_off, ctx->bot.b_off, ctx->bot.u_out, ctx->bot.b_out, ctx->d_rhash, ctx->d_rqlen,
 	                                      ctx->bot.w, ctx->bot.stacks, ctx->d_regs));
-	HIP_TRY(ctx, hipMemcpyAsync(regs, ctx->d_regs, (size_t)n_c * sizeof(chaindp_reg_t), hipMemcpyDeviceToHost, st));
+	if (download) HIP_TRY(ctx, hipMemcpyAsync(regs, ctx->d_regs, (size_t)n_c * sizeof(chaindp_reg_t), hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipStreamSynchronize(st));
+	ctx->regs_resident = true;
 	return CHAINDP_OK;
+}
+
+extern "C" int chaindp_gen_regs(chaindp_ctx_t *ctx, const uint32_t *hash, const int32_t *qlen, chaindp_reg_t *regs)
+{
+	return gen_regs_impl(ctx, hash, qlen, regs, true);
 }
 
 extern "C" int chaindp_est_err(chaindp_ctx_t *ctx, const int64_t *regs_off, chaindp_reg_t *regs, const int32_t *qlen,
@@ -595,6 +615,7 @@ extern "C" int chaindp_est_err(chaindp_ctx_t *ctx, const int64_t *regs_off, chai
 	int rc = regs_per_read_buffers(ctx);
 	if (rc) return rc;
 	hipStream_t st = ctx->stream;
+	ctx->regs_resident = false;                                  // the upload below replaces what chaindp_gen_regs left in d_regs / d_rqlen
 	// every hit's anchors must lie inside its read's chain anchors: checked here, on the host's copy of the offsets
 	{
 		std::vector<int64_t> boff((size_t)R + 1);
@@ -1251,4 +1272,198 @@ extern "C" int chaindp_pipe_release(chaindp_pipe_t *pipe)
 	pipe->tail = (pipe->tail + 1) % pipe->depth;
 	--pipe->inflight;
 	return CHAINDP_OK;
+}
+
+// ---- chain_post + mm_est_err + mm_set_mapq (chaindp_post.hip) -------------------------------------------------------------------
+
+// The integers k in [1, 2^24] where the host's logf((float)k) is not the correctly rounded (float)log((double)k), with the host's value
+// there: built once per process.  Through volatile pointers, so that the compiler neither folds nor substitutes the library calls.
+static std::once_flag g_logf_once;
+static std::vector<uint32_t> g_logf_k;
+static std::vector<float> g_logf_v;
+static float (*volatile g_host_logf)(float) = logf;
+static double (*volatile g_host_log)(double) = log;
+
+static void build_logf_patches()
+{
+	std::call_once(g_logf_once, [] {
+		float (*lf)(float) = g_host_logf;
+		double (*ld)(double) = g_host_log;
+		for (uint32_t k = 1; k <= (uint32_t)POST_LOGF_MAX; ++k) {
+			const float h = lf((float)k), c = (float)ld((double)k);
+			if (memcmp(&h, &c, 4) != 0) { g_logf_k.push_back(k); g_logf_v.push_back(h); }
+		}
+	});
+}
+
+extern "C" int64_t chaindp_post_logf_patches(uint32_t *k, float *v, int64_t cap)
+{
+	build_logf_patches();
+	const int64_t n = (int64_t)g_logf_k.size();
+	for (int64_t i = 0; i < n && i < cap; ++i) { if (k) k[i] = g_logf_k[(size_t)i]; if (v) v[i] = g_logf_v[(size_t)i]; }
+	return n;
+}
+
+static int post_logf_upload(chaindp_ctx *ctx)
+{
+	if (ctx->n_logf >= 0) return CHAINDP_OK;
+	build_logf_patches();
+	const size_t n = g_logf_k.size();
+	HIP_TRY(ctx, bot_alloc(ctx, ctx->d_logf_k, (n ? n : 1) * 4));
+	HIP_TRY(ctx, bot_alloc(ctx, ctx->d_logf_v, (n ? n : 1) * 4));
+	if (n) {
+		HIP_TRY(ctx, hipMemcpy(ctx->d_logf_k, g_logf_k.data(), n * 4, hipMemcpyHostToDevice));
+		HIP_TRY(ctx, hipMemcpy(ctx->d_logf_v, g_logf_v.data(), n * 4, hipMemcpyHostToDevice));
+	}
+	ctx->n_logf = (int)n;
+	return CHAINDP_OK;
+}
+
+extern "C" int64_t chaindp_post_logf_selftest(chaindp_ctx_t *ctx, int32_t kmax)
+{
+	if (!ctx) return CHAINDP_ERR_ARG;
+	if (kmax < 1 || kmax > POST_LOGF_MAX) { ctx->err = "kmax must lie in [1, 2^24]"; return CHAINDP_ERR_ARG; }
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	int rc = post_logf_upload(ctx);
+	if (rc) return rc;
+	float *d_out = nullptr;
+	HIP_TRY(ctx, hipMalloc(&d_out, (size_t)kmax * 8));
+	int32_t *d_term = (int32_t*)(d_out + kmax);
+	std::vector<float> dev((size_t)kmax);
+	std::vector<int32_t> term((size_t)kmax);
+	hipError_t e = chaindp::launch_post_logf_probe(ctx->stream, kmax, ctx->d_logf_k, ctx->d_logf_v, ctx->n_logf, d_out, d_term);
+	if (e == hipSuccess) e = hipMemcpyAsync(dev.data(), d_out, (size_t)kmax * 4, hipMemcpyDeviceToHost, ctx->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(term.data(), d_term, (size_t)kmax * 4, hipMemcpyDeviceToHost, ctx->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	(void)hipFree(d_out);
+	if (e != hipSuccess) { ctx->err = std::string("logf self-test: ") + hipGetErrorString(e); return CHAINDP_ERR_HIP; }
+	float (*lf)(float) = g_host_logf;
+	int64_t bad = 0;
+	for (int32_t k = 1; k <= kmax; ++k) {
+		const float h = lf((float)k);
+		const int t = (int)(4.343f * h + .499f);                     // hit.c:474 as the host evaluates it: float multiply, float add
+		bad += memcmp(&h, &dev[(size_t)k - 1], 4) != 0 || t != term[(size_t)k - 1];
+	}
+	return bad;
+}
+
+static chaindp::PostOpt to_post_opt(const chaindp_post_opt_t *o)
+{
+	chaindp::PostOpt p;
+	p.flag = o->flag; p.mask_level = o->mask_level; p.pri_ratio = o->pri_ratio; p.best_n = o->best_n; p.min_diff = o->min_diff;
+	p.sub_diff = o->sub_diff; p.max_join_long = o->max_join_long; p.max_join_short = o->max_join_short;
+	p.min_join_flank_sc = o->min_join_flank_sc; p.min_cnt = o->min_cnt; p.min_chain_score = o->min_chain_score; p.match_sc = o->match_sc;
+	p.is_sr = o->is_sr;
+	return p;
+}
+
+extern "C" int chaindp_chain_post(chaindp_ctx_t *ctx, const chaindp_post_opt_t *opt, const int32_t *qlen, const int32_t *rep_len,
+                                  const int32_t *ref_len, int32_t n_ref, const int64_t *mini_pos_off, const uint64_t *mini_pos,
+                                  int64_t *regs_off, chaindp_reg_t *regs, int64_t regs_cap, int64_t *a_off, chaindp_anchor_t *a)
+{
+	if (!ctx) return CHAINDP_ERR_ARG;
+	if (!opt || !regs_off || regs_cap < 0 || (regs_cap > 0 && !regs) || n_ref < 0 || (n_ref > 0 && !ref_len) || (a && !a_off)) {
+		ctx->err = "NULL argument"; return CHAINDP_ERR_ARG;
+	}
+	if (ctx->bot_n_reads < 0 || ctx->bot_n_reads != ctx->n_reads || !ctx->bot.has || !ctx->regs_resident) {
+		ctx->err = "chaindp_chain_post needs the hits of a chaindp_gen_regs on this batch (a chaindp_est_err since has replaced them)";
+		return CHAINDP_ERR_ARG;
+	}
+	const int64_t R = ctx->bot_n_reads, n_c = ctx->bot_n_chains, n_b = ctx->bot_n_b;
+	const bool do_mapq = !(opt->flag & CHAINDP_F_CIGAR), do_err = !opt->is_sr;
+	hipStream_t st = ctx->stream;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	// single-segment reads only (mm_select_sub_multi, mm_seg_gen and mm_pair are not here)
+	if (ctx->ran_par.n_segs > 1 && !ctx->has_n_segs) { ctx->err = "chaindp_chain_post takes single-segment reads only (n_segs > 1)"; return CHAINDP_ERR_ARG; }
+	if (ctx->has_n_segs && R > 0) {
+		std::vector<int32_t> ns((size_t)R);
+		HIP_TRY(ctx, hipMemcpyAsync(ns.data(), ctx->d_n_segs, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(ctx, hipStreamSynchronize(st));
+		for (int32_t v : ns) if (v > 1) { ctx->err = "chaindp_chain_post takes single-segment reads only (n_segs > 1)"; return CHAINDP_ERR_ARG; }
+	}
+	if (R == 0) { regs_off[0] = 0; if (a_off) a_off[0] = 0; return CHAINDP_OK; }
+	if (n_c == 0) {
+		for (int64_t r = 0; r <= R; ++r) regs_off[r] = 0;
+		if (a_off) for (int64_t r = 0; r <= R; ++r) a_off[r] = 0;
+		return CHAINDP_OK;
+	}
+	const bool mp_given = mini_pos != nullptr || mini_pos_off != nullptr;
+	if (do_err && !mp_given && (!ctx->mp_resident || !ctx->d_mp_off)) { ctx->err = "no resident mini_pos: pass the arrays, or collect the seeds with chaindp_collect_seeds"; return CHAINDP_ERR_ARG; }
+	if (do_err && mp_given && !mini_pos_off) { ctx->err = "mini_pos without offsets"; return CHAINDP_ERR_ARG; }
+	if (do_mapq && !rep_len && !ctx->mp_resident) { ctx->err = "no resident rep_len: pass it, or collect the seeds with chaindp_collect_seeds"; return CHAINDP_ERR_ARG; }
+	int rc = regs_per_read_buffers(ctx);
+	if (rc) return rc;
+	if ((rc = post_logf_upload(ctx)) != CHAINDP_OK) return rc;
+	const size_t RB = (size_t)ctx->cap_reads + 2;
+	if (!ctx->d_post_off) {
+		HIP_TRY(ctx, bot_alloc(ctx, ctx->d_post_off, RB * 8)); HIP_TRY(ctx, bot_alloc(ctx, ctx->d_post_tile, (RB / 1024 + 2) * 8));
+		HIP_TRY(ctx, bot_alloc(ctx, ctx->d_post_qlen, RB * 4)); HIP_TRY(ctx, bot_alloc(ctx, ctx->d_post_rep, RB * 4));
+		HIP_TRY(ctx, bot_alloc(ctx, ctx->d_post_err, 4));
+	}
+	HIP_TRY(ctx, regs_grow(ctx, ctx->d_post_stage, ctx->post_stage_cap, (size_t)n_c * sizeof(chaindp_reg_t)));
+	HIP_TRY(ctx, regs_grow(ctx, ctx->d_post_out, ctx->post_out_cap, (size_t)n_c * sizeof(chaindp_reg_t)));
+	HIP_TRY(ctx, regs_grow(ctx, ctx->d_post_sq, ctx->post_sq_cap, (size_t)(n_b > 0 ? n_b : 1) * 16));
+	HIP_TRY(ctx, regs_grow(ctx, ctx->d_post_scratch, ctx->post_scratch_cap, (size_t)n_c * POST_SCRATCH_INTS * 4));
+	const int32_t *d_qlen = ctx->d_rqlen;
+	if (qlen) { HIP_TRY(ctx, hipMemcpyAsync(ctx->d_post_qlen, qlen, (size_t)R * 4, hipMemcpyHostToDevice, st)); d_qlen = ctx->d_post_qlen; }
+	const int32_t *d_rep = ctx->d_rep_len;
+	if (rep_len) { HIP_TRY(ctx, hipMemcpyAsync(ctx->d_post_rep, rep_len, (size_t)R * 4, hipMemcpyHostToDevice, st)); d_rep = ctx->d_post_rep; }
+	HIP_TRY(ctx, hipMemsetAsync(ctx->d_post_err, 0, 4, st));
+	const chaindp::PostOpt po = to_post_opt(opt);
+	HIP_TRY(ctx, chaindp::launch_post_read(st, R, ctx->bot.chains_off, ctx->bot.b_off, ctx->bot.b_out, ctx->d_regs, d_qlen, po,
+	                                       (int32_t*)ctx->d_post_scratch, ctx->d_post_stage, ctx->d_post_sq, ctx->d_post_off));
+	HIP_TRY(ctx, chaindp::launch_scan_u64(st, R, ctx->d_post_off, ctx->d_post_tile, ctx->d_post_off + R));
+	HIP_TRY(ctx, chaindp::launch_post_scatter(st, R, ctx->bot.chains_off, ctx->d_post_off, ctx->d_post_stage, ctx->d_post_out));
+	HIP_TRY(ctx, hipMemcpyAsync(regs_off, ctx->d_post_off, (size_t)(R + 1) * 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(ctx, hipStreamSynchronize(st));
+	const int64_t n_out = regs_off[R];
+	if (n_out > regs_cap) { ctx->err = "more hits than regs has room for (regs_off is valid)"; return CHAINDP_ERR_CAPACITY; }
+	if (do_err && n_out > 0) {
+		const int64_t *d_mpo = ctx->d_mp_off;
+		const unsigned long long *d_mp = ctx->d_mini_pos;
+		if (mp_given) {
+			const int64_t n_mp = mini_pos_off[R];
+			if (n_mp < 0 || (n_mp > 0 && !mini_pos)) { ctx->err = "mini_pos announced but absent"; return CHAINDP_ERR_ARG; }
+			HIP_TRY(ctx, regs_grow(ctx, ctx->d_mp_up, ctx->mp_up_cap, (size_t)(n_mp > 0 ? n_mp : 1) * 8));
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mp_off_up, mini_pos_off, (size_t)(R + 1) * 8, hipMemcpyHostToDevice, st));
+			if (n_mp > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mp_up, mini_pos, (size_t)n_mp * 8, hipMemcpyHostToDevice, st));
+			d_mpo = ctx->d_mp_off_up; d_mp = (const unsigned long long*)ctx->d_mp_up;
+		}
+		HIP_TRY(ctx, regs_grow(ctx, ctx->d_ref_len, ctx->ref_len_cap, (size_t)(n_ref > 0 ? n_ref : 1) * 4));
+		if (n_ref > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ref_len, ref_len, (size_t)n_ref * 4, hipMemcpyHostToDevice, st));
+		// k_regs_div over the packed output, with the anchors as chain_post left them (mm_est_err at map.c:872)
+		HIP_TRY(ctx, chaindp::launch_est_err(st, R, n_out, (const int64_t*)ctx->d_post_off, ctx->bot.b_off, ctx->d_post_sq, d_qlen,
+		                                     (const int32_t*)ctx->d_ref_len, n_ref, d_mpo, d_mp, ctx->d_sum_k, ctx->d_post_out, nullptr));
+	}
+	if (do_mapq && n_out > 0)
+		HIP_TRY(ctx, chaindp::launch_post_mapq(st, R, ctx->d_post_off, d_rep, opt->min_chain_score, ctx->d_logf_k, ctx->d_logf_v, ctx->n_logf,
+		                                       ctx->d_post_out, ctx->d_post_err));
+	int32_t err = 0;
+	if (n_out > 0) HIP_TRY(ctx, hipMemcpyAsync(regs, ctx->d_post_out, (size_t)n_out * sizeof(chaindp_reg_t), hipMemcpyDeviceToHost, st));
+	if (a_off) HIP_TRY(ctx, hipMemcpyAsync(a_off, ctx->bot.b_off, (size_t)(R + 1) * 8, hipMemcpyDeviceToHost, st));
+	if (a && n_b > 0) HIP_TRY(ctx, hipMemcpyAsync(a, ctx->d_post_sq, (size_t)n_b * 16, hipMemcpyDeviceToHost, st));
+	HIP_TRY(ctx, hipMemcpyAsync(&err, ctx->d_post_err, 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(ctx, hipStreamSynchronize(st));
+	if (err) { ctx->err = "a score or n_sub + 1 above 2^24: beyond the logf patch list"; return CHAINDP_ERR_CAPACITY; }
+	return CHAINDP_OK;
+}
+
+extern "C" int chaindp_map_reads(chaindp_ctx_t *ctx, const chaindp_index_t *ix, int flag, int max_occ, const chaindp_params_t *par, int min_cnt,
+                                 const chaindp_post_opt_t *opt, int64_t n_reads, const int64_t *mini_off, const chaindp_anchor_t *mini, const uint32_t *bid,
+                                 const int32_t *qlen, const uint32_t *hash, const int32_t *ref_len, int32_t n_ref, int64_t *regs_off, chaindp_reg_t *regs,
+                                 int64_t regs_cap, int32_t *rep_len, int64_t *n_anchors)
+{
+	if (!ctx) return CHAINDP_ERR_ARG;
+	int rc = check_params(ctx, par);
+	if (rc) return rc;
+	if (!opt || !regs_off || regs_cap < 0 || (regs_cap > 0 && !regs) || (n_reads > 0 && !hash)) { ctx->err = "NULL output, hash or opt"; return CHAINDP_ERR_ARG; }
+	if (par->n_segs > 1) { ctx->err = "chaindp_map_reads takes single-segment reads only (n_segs > 1)"; return CHAINDP_ERR_ARG; }
+	// the stages of chaindp_map_batch, with the hits left in HBM, then chain_post on them
+	if ((rc = collect_seeds_impl(ctx, ix, flag, max_occ, n_reads, mini_off, mini, nullptr, bid, qlen, nullptr, nullptr, rep_len, nullptr)) != CHAINDP_OK) return rc;
+	if (n_anchors) *n_anchors = ctx->total;
+	if ((rc = chaindp_run_full(ctx, par)) != CHAINDP_OK) return rc;
+	std::vector<int64_t> c_off((size_t)(n_reads > 0 ? n_reads + 1 : 1)), b_off(c_off.size());
+	if ((rc = chaindp_backtrack(ctx, par, min_cnt, c_off.data(), nullptr, b_off.data(), nullptr)) != CHAINDP_OK) return rc;
+	if ((rc = gen_regs_impl(ctx, hash, qlen, nullptr, false)) != CHAINDP_OK) return rc;
+	return chaindp_chain_post(ctx, opt, nullptr, nullptr, ref_len, n_ref, nullptr, nullptr, regs_off, regs, regs_cap, nullptr, nullptr);
 }

@@ -156,6 +156,27 @@ hipError_t launch_est_err(hipStream_t st, int64_t n_reads, int64_t n_regs, const
                           const int32_t *d_qlen, const int32_t *d_ref_len, int32_t n_ref, const int64_t *d_mp_off, const unsigned long long *d_mini_pos,
                           unsigned long long *d_sum_k, void *d_regs, int32_t *d_counts);
 
+// chain_post + mm_set_mapq (map.c:238-247, hit.c:109-480): chaindp_post.hip
+#define POST_LDS_CAP 256                 // reads with more hits keep their work arrays in global scratch (20 ints per hit)
+#define POST_LOGF_MAX (1 << 24)          // the logf patch list covers the integers up to here
+#define POST_F_SPLICE 0x080
+#define POST_F_NO_LJOIN 0x400
+#define POST_F_SR 0x1000
+#define POST_F_ALL_CHAINS 0x800000
+#define POST_SCRATCH_INTS 20             // global scratch per hit of a read above POST_LDS_CAP
+struct PostOpt {                         // chaindp_post_opt_t
+	int32_t flag;
+	float mask_level, pri_ratio;
+	int32_t best_n, min_diff, sub_diff, max_join_long, max_join_short, min_join_flank_sc, min_cnt, min_chain_score, match_sc, is_sr;
+};
+hipError_t launch_post_read(hipStream_t st, int64_t n_reads, const int64_t *d_chains_off, const int64_t *d_b_off, const void *d_b, const void *d_regs,
+                            const int32_t *d_qlen, const PostOpt &o, int32_t *d_scratch, void *d_stage, void *d_sq, unsigned long long *d_n_out);
+hipError_t launch_post_scatter(hipStream_t st, int64_t n_reads, const int64_t *d_chains_off, const unsigned long long *d_out_off, const void *d_stage,
+                               void *d_out);
+hipError_t launch_post_mapq(hipStream_t st, int64_t n_reads, const unsigned long long *d_out_off, const int32_t *d_rep_len, int min_chain_sc,
+                            const uint32_t *d_pk, const float *d_pv, int n_patch, void *d_out, int32_t *d_err);
+hipError_t launch_post_logf_probe(hipStream_t st, int kmax, const uint32_t *d_pk, const float *d_pv, int n_patch, float *d_out, int32_t *d_term);
+
 // seed collection on the GPU (reference map.c:112-236 over the FPGA index image, index.c:603-720): chaindp_seed.hip
 // The four blobs of the image, as index.c:603-720 writes them:
 //   B: per hash bucket 16 bytes: w0 = (p_off & 0xff) << 56 | n_buckets << 24;  w1 = h_off << 28 | p_off >> 8

@@ -35,3 +35,42 @@ def preset(name, **overrides):
     d = dict(PRESETS[name])
     d.update(overrides)
     return ChainParams(**d)
+
+
+# ---- chain_post / mm_set_mapq options (chaindp_post_opt_t) ---------------------------------------------------------------
+
+MM_F_NO_DIAG, MM_F_NO_DUAL, MM_F_CIGAR = 0x001, 0x002, 0x004          # minimap.h:8-10
+MM_F_SPLICE, MM_F_NO_LJOIN, MM_F_SR = 0x080, 0x400, 0x1000            # minimap.h:15,18,20
+MM_F_ALL_CHAINS = 0x800000                                            # minimap.h:31
+
+
+class PostOpt(C.Structure):
+    """Mirror of chaindp_post_opt_t (include/chaindp.h): the mm_mapopt_t fields chain_post, mm_est_err and mm_set_mapq read."""
+    _fields_ = [("flag", C.c_int32), ("mask_level", C.c_float), ("pri_ratio", C.c_float)] + \
+               [(k, C.c_int32) for k in ("best_n", "min_diff", "sub_diff", "max_join_long", "max_join_short", "min_join_flank_sc",
+                                          "min_cnt", "min_chain_score", "match_sc", "is_sr")]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return "PostOpt(" + ", ".join(f"{k}={v}" for k, v in self.asdict().items()) + ")"
+
+
+# mm_mapopt_init (options.c:28-45): mask_level, pri_ratio, best_n, the join limits, min_cnt, min_chain_score, a = 2, b = 4
+_POST_DEFAULTS = dict(flag=0, mask_level=0.5, pri_ratio=0.8, best_n=5, max_join_long=20000, max_join_short=2000, min_join_flank_sc=1000,
+                      min_cnt=3, min_chain_score=40, match_sc=2, sub_diff=2 * 2 + 4, is_sr=0)
+# mm_set_opt (options.c:84-96): k of the preset's index (min_diff = mi->k * 2, map.c:242), the map options it changes
+POST_PRESETS = {
+    "map-ont": dict(min_diff=2 * 15),
+    "map-pb": dict(min_diff=2 * 19),
+    "ava-ont": dict(min_diff=2 * 15, flag=MM_F_ALL_CHAINS | MM_F_NO_DIAG | MM_F_NO_DUAL | MM_F_NO_LJOIN, min_chain_score=100, pri_ratio=0.0),
+    "ava-pb": dict(min_diff=2 * 19, flag=MM_F_ALL_CHAINS | MM_F_NO_DIAG | MM_F_NO_DUAL | MM_F_NO_LJOIN, min_chain_score=100, pri_ratio=0.0),
+}
+
+
+def post_preset(name, **overrides):
+    d = dict(_POST_DEFAULTS)
+    d.update(POST_PRESETS[name])
+    d.update(overrides)
+    return PostOpt(**d)
