@@ -406,6 +406,19 @@ class Device:
         self._lib.chaindp_debug_quad_took.argtypes = [C.c_void_p]
         return int(self._lib.chaindp_debug_quad_took(self._ctx)) == 1
 
+    def set_twin_tables(self, two=True):
+        """Test hook: True keeps k_chain_twin on its layout with a cost table per half even where the batch has one table key (the
+        layout with one table per wave takes such batches otherwise); False lets the device decide."""
+        self._lib.chaindp_debug_set_twin_tables.restype = C.c_int
+        self._lib.chaindp_debug_set_twin_tables.argtypes = [C.c_void_p, C.c_int]
+        self._check(self._lib.chaindp_debug_set_twin_tables(self._ctx, int(bool(two))))
+
+    def twin_tables(self):
+        """Which layout k_chain_twin ran the last batch with (test hook): 1 one cost table per wave, 2 one per half, 0 neither."""
+        self._lib.chaindp_debug_twin_tables.restype = C.c_int
+        self._lib.chaindp_debug_twin_tables.argtypes = [C.c_void_p]
+        return int(self._lib.chaindp_debug_twin_tables(self._ctx))
+
     def set_twin_handover(self, mode=0):
         """Test hook: what k_chain_twin hands over to k_chain_units whatever the units look like -- 0 nothing extra, 1 every unit
         untouched, 2 every unit after its first 64-anchor tile (k_chain_units resumes behind the flushed tiles)."""

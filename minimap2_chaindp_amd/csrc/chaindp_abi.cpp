@@ -43,13 +43,14 @@ struct chaindp_ctx {
 	chaindp::UnitAux *d_unit_aux = nullptr;   // per unit, beside d_units: what k_chain_twin needs to pick it up without further loads
 	Unit *d_left = nullptr;               // units the two-per-wave kernel hands over to k_chain_units
 	unsigned long long *d_left_cnt = nullptr;   // [0] handed-over count | the twin / quad kernel's queue << 32; [1] count of d_deep; [2] k_chain_dense1's two queues;
-	                                            // [3] route: 1 = k_chain_quad took the batch
+	                                            // [3] route: 1 = k_chain_quad took the batch, 2 / 3 = k_chain_twin with one / two cost tables
 	Unit *d_deep = nullptr;               // units k_chain_units hands over to its k_chain_dense (scans that keep reaching past the ring)
 	int deep_route = 0;                   // test hook: 1 k_chain_dense, 2 k_chain_dense1 whatever the batch looks like
 	int deep_eager = 0;                   // test hook: hand over any unit with a few deep scans, whatever its length
 	bool deep_handover = true;            // CHAINDP_NO_DEEP_HANDOVER (diagnostic / A-B): every unit stays in the launch that took it
 	bool use_quad = false;                // CHAINDP_QUAD=1 / chaindp_debug_set_quad (A/B, tests): one-table batches of ordinary units four per wave
 	                                      // (k_chain_quad: correct, measured slower than k_chain_twin -- DESIGN.md section 6 -- so off by default)
+	int twin_two_tables = 0;              // chaindp_debug_set_twin_tables (tests): 1 keeps one-key batches on k_chain_twin's two-table layout
 	int twin_force_left = 0;              // CHAINDP_TWIN_FORCE_LEFT / chaindp_debug_set_twin_handover (tests): 1 k_chain_twin hands every unit
 	                                      // over untouched, 2 after its first tile (k_chain_units resumes there); the variable is read once, at chaindp_create
 	int variant = 0;                      // 0: k_chain_twin + k_chain_units for the rest; 1: k_chain_units, general variant; 2: k_chain_units only
@@ -305,7 +306,8 @@ static int run_on_stream(chaindp_ctx *ctx, const chaindp_params_t *par, int64_t 
 			                                        (unsigned int*)ctx->d_left_cnt + 1, route, ctx->twin_force_left, total));
 		HIP_TRY(ctx, chaindp::launch_chain_twin(st, qt, total / 2, d_off, d_a, ctx->d_sumq, lut, lut_stride, ctx->d_units, ctx->d_counters,
 		                                        d_f, d_p, d_v, ctx->d_first_child, ctx->cmp.flags, ctx->d_left, (unsigned int*)ctx->d_left_cnt,
-		                                        ctx->twin_force_left, total, ctx->d_unit_aux, route, ctx->d_twin_queue));
+		                                        ctx->twin_force_left, total, ctx->d_unit_aux, ctx->pre.key_range, route, ctx->d_twin_queue,
+		                                        ctx->twin_two_tables));
 		const int64_t left_grid = total / 2 < 32768 ? total / 2 : 32768;
 		HIP_TRY(ctx, chaindp::launch_chain(st, ctx->ring, q, left_grid, d_off, d_a, d_n_segs, ctx->d_sumq, lut, lut_stride, ctx->d_left,
 		                                   ctx->d_left_cnt, d_f, d_p, d_v, ctx->d_tg, ctx->epoch, ctx->d_first_child, ctx->cmp.flags,
@@ -678,7 +680,32 @@ extern "C" int chaindp_debug_quad_took(chaindp_ctx_t *ctx)
 	unsigned long long r = 0;
 	if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
 	    hipMemcpy(&r, ctx->d_left_cnt + 3, sizeof(r), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-	return (uint32_t)r != 0;
+	return (uint32_t)r == 1u;
+}
+
+// test hook (not in the public header): 1 keeps k_chain_twin on its layout with a cost table per half even where the batch has one
+// table key (which otherwise takes the layout with one table per wave); 0 (default) lets the device decide
+extern "C" int chaindp_debug_set_twin_tables(chaindp_ctx_t *ctx, int two)
+{
+	if (!ctx) return CHAINDP_ERR_ARG;
+	ctx->twin_two_tables = two != 0;
+	return CHAINDP_OK;
+}
+
+// test hook (not in the public header; no GPU needed): k_chain_twin's LDS bytes per workgroup with one cost table per wave (one_table
+// != 0) or one per half, and the most workgroups per CU its launch asks for (samegap: max_dist_y >= max_dist_x)
+extern "C" int64_t chaindp_debug_twin_lds_bytes(int one_table) { return (int64_t)chaindp::twin_lds_bytes(one_table != 0); }
+extern "C" int chaindp_debug_twin_max_wg_per_cu(int samegap, int one_table) { return chaindp::twin_max_wg_per_cu(samegap != 0, one_table != 0); }
+
+// test hook (not in the public header): which layout k_chain_twin ran the last batch with -- 1 one cost table per wave, 2 one per
+// half, 0 neither (k_chain_quad took the batch, or the twin kernel declined it as a whole)
+extern "C" int chaindp_debug_twin_tables(chaindp_ctx_t *ctx)
+{
+	if (!ctx || !ctx->d_left_cnt) return -1;
+	unsigned long long r = 0;
+	if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
+	    hipMemcpy(&r, ctx->d_left_cnt + 3, sizeof(r), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+	return (uint32_t)r == 2u ? 1 : (uint32_t)r == 3u ? 2 : 0;
 }
 
 // test hook (not in the public header): what k_chain_twin hands over whatever the units look like -- 0 nothing extra, 1 every unit

@@ -97,13 +97,18 @@ hipError_t launch_chain_dense1(hipStream_t st, const Params &par, int64_t max_un
                                int32_t *d_f, int32_t *d_p, int32_t *d_v, int32_t *d_first_child, uint8_t *d_flags);
 
 // Two units per wave, 32 lanes each (chaindp_twin.hip): takes the ordinary units, appends the others (general-variant reads,
-// scans that reach beyond 64 predecessors) to d_left / *d_left_cnt (low 32 bits = count), which launch_chain then runs.
+// scans that reach beyond 64 predecessors) to d_left / *d_left_cnt (low 32 bits = count), which launch_chain then runs.  Two LDS
+// layouts, both launched: one cost table per wave (32 workgroups per CU) for batches whose units share one table key (d_key_range),
+// else one per half (24 per CU).  *d_route (zeroed with the batch): 1 k_chain_quad took the batch, 2 the one-table layout, 3 the
+// two-table layout.  two_tables != 0 (tests) keeps every batch on the two-table layout.
 hipError_t launch_chain_twin(hipStream_t st, const Params &par, int64_t max_units, const int64_t *d_off, const void *d_a,
                              const unsigned long long *d_sumq, const uint16_t *d_lut, int lut_stride, const Unit *d_units,
                              const unsigned long long *d_counters, int32_t *d_f, int32_t *d_p, int32_t *d_v,
                              int32_t *d_first_child, uint8_t *d_flags, Unit *d_left, unsigned int *d_left_cnt, int force_left, int64_t total,
-                             const UnitAux *d_unit_aux, const unsigned int *d_route = nullptr, unsigned int *d_queue = nullptr   /* 8 x 64 words: the grab counters */);
-size_t twin_lds_bytes();
+                             const UnitAux *d_unit_aux, const unsigned int *d_key_range, unsigned int *d_route,
+                             unsigned int *d_queue /* 8 x 64 words: the grab counters */, int two_tables);
+size_t twin_lds_bytes(bool one_table);
+int twin_max_wg_per_cu(bool samegap, bool one_table);
 
 // Four units per wave, 16 lanes each, two predecessors per lane (chaindp_quad.hip): takes a batch of ordinary units whose reads all
 // have the same cost table (key_range: PrepassScratch::key_range) and says so in *d_route; otherwise it leaves the batch to

@@ -55,6 +55,26 @@ __device__ __forceinline__ uint32_t tw_sad(uint32_t a, uint32_t b, uint32_t c)
 	return d;
 }
 
+// |a - b| in one instruction
+__device__ __forceinline__ uint32_t tw_absdiff(uint32_t a, uint32_t b)
+{
+	uint32_t d = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+	asm("v_sad_u32 %0, %1, %2, 0" : "=v"(d) : "v"(a), "v"(b));
+#endif
+	return d;
+}
+
+// b - a - 1 in one instruction ((a ^ ~0) + b)
+__device__ __forceinline__ uint32_t tw_sub_m1(uint32_t b, uint32_t a)
+{
+	uint32_t d = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+	asm("v_xad_u32 %0, %1, -1, %2" : "=v"(d) : "v"(a), "v"(b));
+#endif
+	return d;
+}
+
 // lane masks straight from a vector compare (v_cmp_*_e64 into an SGPR pair, no bool in between)
 #define TW_ULT(a, b) __builtin_amdgcn_uicmp((unsigned)(a), (unsigned)(b), 36)
 #define TW_EQ(a, b)  __builtin_amdgcn_uicmp((unsigned)(a), (unsigned)(b), 32)

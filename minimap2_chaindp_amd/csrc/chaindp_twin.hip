@@ -21,18 +21,22 @@
 // (the PF ring holds f - 1, the current anchor's floor is q_span - 1; chain.c:251,274 compare the same way when both sides are
 // shifted), so that a pass needs q_span - 1 only; reads with a zero q_span go to k_chain_units.
 //
-// LDS per wave (dynamic segment, starts at byte 0; h = half):
-//   XY  [128 slots][2 halves] 8 B   x.lo+1, qpos+1 of anchor (slot = i & 127), written a whole tile at a time
+// LDS per wave (dynamic segment, starts at byte 0; h = half).  Two layouts (TwLayout): one cost table per wave, for batches whose
+// units all have one table key, and one per half, for the others:
+//   XY  [128 slots][2 halves] 8 B   x.lo+1, qpos+1 of anchor (slot = i & 127), written a whole tile at a time; with one table a pass
+//                                   reads its own anchor from here too (the current tile is in the ring)
 //   PF  [ 64 slots][2 halves] 8 B   4*p (unit-relative, -4 = none), f - 1 of anchor (slot = i & 63)
 //   V   [ 64 slots][2 halves] 4 B   v | "emitted at its own step" << 31
-//   XQ  [2 halves][64] 8 B          the current tile's anchors as a pass wants them: x.lo, qpos
-//   LUT [2 halves][512] int8        the read's table of 1 - cost (reads whose costs do not fit a byte go to k_chain_units)
+//   XQ  [2 halves][64] 8 B          two tables only: the current tile's anchors as a pass wants them, x.lo, qpos
+//   LUT [1 or 2][512] int8          the table of 1 - cost (reads whose costs do not fit a byte go to k_chain_units)
 //   ST  [2 halves] 56 B             the half's cold state (TwinCold) and what a scan carries into its second chunk
 //   MK  [2 halves][65] 4 B          marks by distance: word d-1 holds the scan tag of the anchor d behind; word 64 = sink
-//   SP  [2 halves][64] 1 B          q_span - 1 of the current tile's anchors (entry n of XQ at byte a has its SP byte at a / 8 + const)
-//   KEY [2 halves] 4 B              which read's table the half's LUT holds (reads with the same avg_qspan share it)
-// 6400 bytes.  LDS is handed out in pieces of 1280 bytes on this chip (tools/lds_occupancy_probe.hip measures how many workgroups
-// a CU holds; the occupancy API does not know): 6400 bytes are the most that leave 24 waves per CU, i.e. six per SIMD.
+//   SP  128 B                       q_span - 1 of the current tile's anchors: one table, byte 2 (i & 63) + h (its XY address / 8);
+//                                   two tables, [h][entry] (its XQ address / 8 + const)
+//   KEY [2 halves] 4 B              which read's table the LUT holds (reads with the same avg_qspan share it; one word per table)
+// 4864 bytes with one table, 6400 with two.  LDS is handed out in pieces of 1280 bytes on this chip (tools/lds_occupancy_probe.hip
+// measures how many workgroups a CU holds; the occupancy API does not know): 5120 bytes leave 32 workgroups per CU (eight waves per
+// SIMD), 6400 bytes 25 (the two-table layout runs 24: six waves per SIMD, whose registers keep a tile prefetch).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <limits.h>
@@ -48,19 +52,35 @@ namespace chaindp {
 #define TW_XY 0u
 #define TW_PF 2048u
 #define TW_V 3072u
-#define TW_XQ 3584u
-#define TW_XQ_HALF 512u
-#define TW_LUT 4608u
-#define TW_LUT_HALF 512u
-#define TW_ST 5632u
+#define TW_LUT_BYTES 512u                // one table (bw + 1 <= 512 entries)
 #define TW_ST_HALF 56u
-#define TW_MK 5744u
 #define TW_MK_HALF 260u
-#define TW_SP 6264u
-#define TW_SP_HALF 64u
-#define TW_SP_OF_XQ (TW_SP - TW_XQ / 8u)  // SP address = (XQ address >> 3) + this
-#define TW_KEY 6392u                    // [2 halves] 4 B: key of the cost table the half's LUT holds (UnitAux::lutkey)
-#define TW_LDS_BYTES 6400u
+// XY, PF and V first (XY and PF at offsets 0 and 2048: the bank pattern of a pass' two ring reads), then:
+//   one table per wave:  LUT [512], ST, MK, SP [64 slots][2 halves], KEY                     4864 bytes
+//   one table per half:  XQ [2][64] 8 B, LUT [2][512], ST, MK, SP [2][64], KEY                6400 bytes (the layout before the one-table
+//                        one existed: the pass reads its anchor from XQ, x.lo and qpos as they are)
+template <bool ONE_LUT> struct TwLayout {
+	static constexpr bool HAS_XQ = !ONE_LUT;
+	static constexpr uint32_t XQ = 3584u, XQ_HALF = 512u;                    // (two tables only)
+	static constexpr uint32_t LUT = ONE_LUT ? 3584u : XQ + 2u * XQ_HALF;
+	static constexpr uint32_t LUT_HALF = ONE_LUT ? 0u : TW_LUT_BYTES;        // the second half's table
+	static constexpr uint32_t ST = LUT + (ONE_LUT ? 1u : 2u) * TW_LUT_BYTES;
+	static constexpr uint32_t MK = ST + 2u * TW_ST_HALF;
+	static constexpr uint32_t SP = MK + 2u * TW_MK_HALF;
+	static constexpr uint32_t SP_HALF = ONE_LUT ? 0u : 64u;                 // one table: byte 2 (i & 63) + h; two: [h][entry of XQ]
+	static constexpr uint32_t SP_OF_XQ = SP - XQ / 8u;                        // (two tables) SP address = (XQ address >> 3) + this
+	static constexpr uint32_t KEY = SP + 128u;                                // [2] 4 B: key of the cost table (UnitAux::lutkey); one table: word 0
+	static constexpr uint32_t KEY_HALF = ONE_LUT ? 0u : 4u;
+	static constexpr uint32_t BYTES = KEY + 8u;
+	static_assert(ST % 8u == 0u && MK % 4u == 0u && KEY % 4u == 0u, "cold state is read as 64-bit words, marks and keys as 32-bit");
+};
+static_assert(TwLayout<true>::BYTES == 4864u && TwLayout<true>::BYTES <= 5120u, "one table: 32 workgroups per CU");
+static_assert(TwLayout<false>::BYTES == 6400u, "two tables: 24 workgroups per CU");
+// waves per SIMD each instantiation is compiled for (VGPRs <= 512 / waves, no scratch: tests/test_twin_resources.py).  One table:
+// the LDS allows 32 workgroups per CU, and the registers eight waves per SIMD (seven for max_dist_y < max_dist_x, which carries one more
+// per-lane constant, c_dqoff).  Two tables: the LDS allows 24 workgroups per CU, six waves per SIMD, and the registers at six waves keep
+// the tile prefetch (PF in the kernel).
+template <bool SAMEGAP, bool ONE_LUT> struct TwWaves { static constexpr int N = !ONE_LUT ? 6 : SAMEGAP ? 8 : 7; };
 #define TW_TILE 64                      // anchors a half takes in / flushes at a time
 #define TW_RING 64                      // predecessors a scan can reach in this kernel (two chunks of 32)
 #define TW_QCH 8                        // units a half takes from the queue at a time
@@ -161,15 +181,17 @@ struct TwinArgs {
 	Unit *left;                       // leftover list for k_chain_units
 	unsigned int *left_cnt;
 	unsigned int *queue;              // eight grab counters, 64 words apart (the halves' first grabs are dealt statically: they start behind them)
-	const unsigned int *route;        // *route != 0: k_chain_quad (launched in front of this kernel) has taken the batch
+	const unsigned int *key_range;    // [0] min, [1] max of the units' table keys (prepass)
+	unsigned int *route;              // 1: k_chain_quad took the batch; 2: the one-table layout did; 3: the two-table layout did
+	int two_tables;                   // test switch: 1 keeps a one-key batch on the two-table layout
 	int force_left;                   // test switch: 1 hand every unit over untouched, 2 hand every unit over after its first tile (resumed there)
 	int64_t total;                    // anchors of the batch
 	unsigned long long *stamp;        // diagnostic run (CHAINDP_TWIN_STAMP): per block 8 counters; nullptr otherwise
 };
 
-// the state of a half that only the service path needs lives in LDS (TW_ST + 64 h), so that the pass loop carries
+// the state of a half that only the service path needs lives in LDS (ST + 56 h), so that the pass loop carries
 // nothing but what a pass reads
-struct TwinCold {                     // 40 bytes at TW_ST + 56 h (8-byte aligned: read and written as 64-bit words)
+struct TwinCold {                     // 40 bytes at ST + 56 h (8-byte aligned: read and written as 64-bit words)
 	int64_t next;                     // next unit of this half (grid-stride over pairs)
 	int64_t base;                     // global index of the unit's first anchor
 	uint64_t x_carry;                 // x of the previous tile's last anchor
@@ -180,10 +202,12 @@ struct TwinCold {                     // 40 bytes at TW_ST + 56 h (8-byte aligne
 struct TwinHot {
 	uint32_t S;                       // 16 * jtop + 8h, jtop = i - 1 - 32c: ring offset of lane 0's predecessor
 	uint32_t m4;                      // 4 * (i - 1) + mark base: mark distance base and the scan's tag
-	uint32_t pc, pend;                // XQ entry of the current anchor; end of the tile's entries
+	uint32_t pc;                      // (two tables) XQ entry of the current anchor
+	uint32_t pend;                    // one table: m4 of the tile's last anchor, exhausted once m4 >= pend (0: no tile);
+	                                  // two tables: end of the tile's XQ entries, exhausted once pc >= pend
 };
 // What a scan carries into its second chunk (one scan in thirty) is not worth registers: it sits behind the half's cold state
-// (TW_ST + 56 h + 40): 4 * max_j (-4: none), the running max of the scan (chain.c:274) minus one, n_skip, and the second chunks
+// (ST + 56 h + 40): 4 * max_j (-4: none), the running max of the scan (chain.c:274) minus one, n_skip, and the second chunks
 // the unit has needed so far.
 #define TW_CARRY 40u
 
@@ -214,21 +238,24 @@ struct TwinHot {
 #endif
 #define TW_NOW() __builtin_amdgcn_s_memtime()
 
-template <bool SAMEGAP>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_chain_twin(TwinArgs g)
+// ONE_LUT: the layout with one cost table per wave (TwLayout<true>), for batches whose units all have the same table key; the other
+// instantiation keeps one table per half.  Both are launched; the first that finds the batch to be its own takes it (g.route).
+template <bool SAMEGAP, bool ONE_LUT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAMEGAP, ONE_LUT>::N, TwWaves<SAMEGAP, ONE_LUT>::N))) void k_chain_twin(TwinArgs g)
 {
+	using L = TwLayout<ONE_LUT>;
 	const int lane = threadIdx.x;
 	const bool hi_half = lane >= 32;
 	const int h = lane >> 5, hl = lane & 31;
 
 	// ---- per-lane constants (vector registers on purpose, see TW_VREG)
 	uint32_t L16 = (uint32_t)hl << 4;
-	const uint32_t mkbase = TW_MK + TW_MK_HALF * (uint32_t)h;      // this half's mark words
-	const uint32_t curbase = TW_XQ + TW_XQ_HALF * (uint32_t)h;     // this half's XQ entries
+	const uint32_t mkbase = L::MK + TW_MK_HALF * (uint32_t)h;      // this half's mark words
+	const uint32_t curbase = L::XQ + L::XQ_HALF * (uint32_t)h;     // (two tables) this half's XQ entries
 	uint32_t c_mkbase = mkbase;
 	uint32_t c_far = mkbase + 256u;                                // its sink word
 	uint32_t c_own = mkbase + ((uint32_t)hl << 2);                 // lane's own mark word in chunk 0
-	uint32_t c_lut = TW_LUT + TW_LUT_HALF * (uint32_t)h;
+	uint32_t c_lut = ONE_LUT ? 0u : L::LUT + L::LUT_HALF * (uint32_t)h;   // the half's table base (one table: in the DS offset, LUT_OFF)
 	uint32_t c_8h = (uint32_t)h << 3;
 	uint32_t c_M = (uint32_t)g.par.max_dist_x;
 	uint32_t c_bw = (uint32_t)g.par.bw;
@@ -238,14 +265,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 	int c_ms = g.par.max_skip;
 	int c_min = INT_MIN;
 	int c_Mout = hl == 31 ? g.par.max_dist_x : INT_MAX;            // window test that only the half's last lane can fail
-	uint32_t c_bwl = c_bw + c_lut;                                 // table address of the last entry
+	uint32_t c_bwl = c_bw + c_lut;                                 // table address of the last entry (- LUT_OFF)
 	uint32_t c_cbwl = c_cbw - c_lut;                               // (dd + c_lut) + this = dd + c_cbw
-	TW_VREG(L16); TW_VREG(c_far); TW_VREG(c_own); TW_VREG(c_lut); TW_VREG(c_M);
+	constexpr uint32_t LUT_OFF = ONE_LUT ? L::LUT : 0u;
+	// (one table: c_M and c_ms stay scalar -- only compares read them -- for the registers of the eighth wave)
+	TW_VREG(L16); TW_VREG(c_far); TW_VREG(c_own);
+	if (!ONE_LUT) { TW_VREG(c_M); TW_VREG(c_ms); }
+	if (!ONE_LUT) TW_VREG(c_lut);
 	if (!SAMEGAP) TW_VREG(c_dqoff);
-	TW_VREG(c_ms); TW_VREG(c_min); TW_VREG(c_Mout); TW_VREG(c_bwl); TW_VREG(c_cbwl);
+	TW_VREG(c_min); TW_VREG(c_Mout); TW_VREG(c_bwl); TW_VREG(c_cbwl);
 
 	const uint64_t maxx = (uint64_t)(int64_t)g.par.max_dist_x;
-	if (g.route && *g.route) return;                               // (uniform) the batch went four units per wave
+	// (uniform) which kernel takes the batch: k_chain_quad has written 1 before this kernel starts; the one-table layout takes
+	// batches whose units share one table key and writes 2, which the two-table layout, launched behind it, then finds
+	const uint32_t route = *g.route;
+	if (ONE_LUT ? route == 1u || g.key_range[0] != g.key_range[1] || g.two_tables : route == 1u || route == 2u) return;
 	const int64_t n_units = (int64_t)(uint32_t)g.counters[0];
 	// the kernel's 32-bit differences (and the signed window test) are exact while 129 * (max_dist_x + 1) < 2^31
 	// Units of a few thousand anchors (map-ont shape) are few and each is a long serial chain: two of them side by side gain
@@ -256,14 +290,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 		if (blockIdx.x == 0 && lane == 0) *g.left_cnt = 0xffffffffu;
 		return;
 	}
+	if (blockIdx.x == 0 && lane == 0) *g.route = ONE_LUT ? 2u : 3u;
 	const bool params_ok = g.lut != nullptr && !g.par.is_cdna && g.par.max_dist_x >= 1 && g.par.max_dist_y >= 0 &&
-	                       ((uint64_t)(int64_t)g.par.max_dist_x + 1) * 129ull < (1ull << 31) && g.par.bw + 1 <= (int)TW_LUT_HALF && g.force_left != 1;
+	                       ((uint64_t)(int64_t)g.par.max_dist_x + 1) * 129ull < (1ull << 31) && g.par.bw + 1 <= (int)TW_LUT_BYTES && g.force_left != 1;
 
 	TwinHot u;
-	u.S = 0; u.m4 = 0; u.pc = curbase; u.pend = curbase;
+	u.S = 0; u.m4 = 0; u.pc = L::HAS_XQ ? curbase : 0u; u.pend = u.pc;
 	uint64_t live_m = ~0ull;                                       // halves that still have (or may get) work
 	uint64_t contm = 0;                                            // halves that are in their second (= last) chunk
-	const uint32_t st_addr = TW_ST + TW_ST_HALF * (uint32_t)h;
+	const uint32_t st_addr = L::ST + TW_ST_HALF * (uint32_t)h;
 #define TW_COLD (*TW_LDS(TwinCold, st_addr))
 	// The unit queue.  Eight counters, a cache line apart (one same-address atomic takes ~7.5 ns: 133 M a second for the whole chip
 	// on ONE counter), workgroup b on counter b mod 8.  A half's p-th grab of its counter k is the chunk of TW_QCH units number
@@ -290,22 +325,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 		tw_st64(st_addr + 16u, 0u, 0u); tw_st64(st_addr + 24u, 0u, 0u);                 // x_carry, rel0, room
 		tw_st64(st_addr + 32u, 0u, (uint32_t)-TW_TILE);                                 // read, tile0
 		tw_st64(st_addr + TW_CARRY, 0xfffffffcu, 0u); tw_st64(st_addr + TW_CARRY + 8u, 0u, 0u);   // carry, second chunks so far
-		tw_st32(TW_KEY + 4u * (uint32_t)h, -1);                                         // no table yet (an avg_qspan is never a NaN)
+		tw_st32(L::KEY + 4u * (uint32_t)h, -1);                                         // no table yet (an avg_qspan is never a NaN)
 	}
 	wave_mem_fence();
 
+	// The two-table layout runs at six waves per SIMD (its LDS allows 24 workgroups per CU), which leaves the registers for a tile
+	// prefetch: each half's NEXT tile is requested a tile ahead into registers.  The one-table layout gives those eight registers up
+	// for the seventh and eighth wave and loads a tile when it takes it.
+	constexpr bool PF = !ONE_LUT;
+	uint64_t nx0_x = 0, nx0_y = 0, nx1_x = 0, nx1_y = 0;           // (PF) each half's next tile, one anchor per lane; zeros where the unit has none
+	int32_t pfu0 = -1, pfu1 = -1;                                  // (PF) ... or, when the unit ends with the current tile, the first tile of the half's
+	                                                               // next unit: its first anchor's global index (wave-uniform), -1 = no such tile
+
 	TW_STAMP(unsigned long long st_t0 = 0; unsigned int st_service = 0, st_n_service = 0, st_n_fast = 0, st_flush = 0, st_unit = 0, st_n_unit = 0, st_head = 0, st_take = 0, st_tail = 0;)   // (32-bit sums: a wave's ticks fit, and the build has no registers to spare)
-	uint64_t nx0_x = 0, nx0_y = 0, nx1_x = 0, nx1_y = 0;           // each half's NEXT tile, requested a tile ahead (one anchor per lane; zeros where the unit has none)
-	int32_t pfu0 = -1, pfu1 = -1;                                  // ... or, when the unit ends with the current tile, the first tile of the half's NEXT
-	                                                               // unit: its first anchor's global index (wave-uniform), -1 = the registers hold no such tile
 
 	// One service round for the halves in `svc`, whose tile is exhausted (or which have no unit yet).  One half at a time, by ALL 64
 	// lanes of the wave (a tile is 64 anchors, one per lane): everything that is per half (the cold state, the unit being picked,
 	// loop conditions) is wave-uniform and lives in scalar registers, loads by scalar address go through the scalar cache, and the
 	// loops are scalar branches; what goes back into the half's hot state is selected into its 32 lanes (TW_SEL by `hm`).  Order:
-	// the unit's NEXT tile (requested ahead) is taken first -- before the finished tile's f/p/v are stored, so that nothing waits
-	// for those stores --, then the finished tile is flushed; a half whose unit is over picks its next unit and loads that one's
-	// first tile.  Once per 64 anchors and half.
+	// the unit's next tile is loaded and taken first -- before the finished tile's f/p/v are stored, so that nothing waits for those
+	// stores --, then the finished tile is flushed; a half whose unit is over picks its next unit and loads that one's first tile.
+	// Once per 64 anchors and half.  Where the layout prefetches (PF), the next tile and a successor unit's first tile are already in
+	// registers, requested a tile of passes ago.
 	auto service = [&](uint64_t svc) {
 #if defined(__HIP_DEVICE_COMPILE__)
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // (whatever is outstanding was issued a tile of passes ago: no wait in practice)
@@ -316,32 +357,38 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 			if (((svc >> (32 * hs)) & 1ull) == 0) continue;
 			TW_STAMP_B(const unsigned long long th0 = g.stamp ? TW_NOW() : 0;)
 			const uint64_t hm = hs ? 0xffffffff00000000ull : 0x00000000ffffffffull;   // the lanes that carry this half's hot state
-			const uint32_t sa = TW_ST + TW_ST_HALF * (uint32_t)hs;
-			const uint32_t curb = TW_XQ + TW_XQ_HALF * (uint32_t)hs, spb = TW_SP + TW_SP_HALF * (uint32_t)hs;   // (SP: a byte per anchor)
-			const uint32_t mkb = TW_MK + TW_MK_HALF * (uint32_t)hs, lutb = TW_LUT + TW_LUT_HALF * (uint32_t)hs;
+			const uint32_t sa = L::ST + TW_ST_HALF * (uint32_t)hs, keya = L::KEY + L::KEY_HALF * (uint32_t)hs;
+			const uint32_t mkb = L::MK + TW_MK_HALF * (uint32_t)hs, lutb = L::LUT + L::LUT_HALF * (uint32_t)hs;
+			const uint32_t curb = L::XQ + L::XQ_HALF * (uint32_t)hs, spb = L::SP + L::SP_HALF * (uint32_t)hs;
 			const tw_u32x2 cw0 = tw_ld64(sa), cw1 = tw_ld64(sa + 8u), cw2 = tw_ld64(sa + 16u), cw3 = tw_ld64(sa + 24u), cw4 = tw_ld64(sa + 32u);
 			int64_t c_next = (int64_t)((uint64_t)TW_UNI(cw0.y) << 32 | TW_UNI(cw0.x));
 			int64_t c_base = (int64_t)((uint64_t)TW_UNI(cw1.y) << 32 | TW_UNI(cw1.x));
 			uint64_t c_xcarry = (uint64_t)TW_UNI(cw2.y) << 32 | TW_UNI(cw2.x);
 			int c_rel0 = (int)TW_UNI(cw3.x), c_room = (int)TW_UNI(cw3.y), c_read = (int)TW_UNI(cw4.x), c_tile0 = (int)TW_UNI(cw4.y);
-			const int cnt_prev = (int)(((uint32_t)__builtin_amdgcn_readlane((int)u.pend, 32 * hs) - curb) >> 3);   // anchors of the tile that has just been scored
+			// anchors of the tile a half holds (the one just scored, or the one taken in this call)
+			auto tile_cnt = [&]() -> int {
+				const uint32_t pe = TW_UNI(__builtin_amdgcn_readlane((int)u.pend, 32 * hs));
+				if constexpr (L::HAS_XQ) return (int)((pe - curb) >> 3);
+				else return pe < mkb ? 0 : (int)((pe - mkb) >> 2) + 1 - c_tile0;
+			};
+			const int cnt_prev = tile_cnt();
 			const int slow_h = (int)TW_UNI((uint32_t)tw_ld32(sa + TW_CARRY + 12u));
-			const uint32_t cur_key = TW_UNI((uint32_t)tw_ld32(TW_KEY + 4u * (uint32_t)hs));
+			const uint32_t cur_key = TW_UNI((uint32_t)tw_ld32(keya));
 			const int tile_prev = c_tile0, rel0_prev = c_rel0;
 			const int64_t base_prev = c_base;
 			bool live = true;
-			// The half's next unit (and the one after it), when this call will need them -- the unit ends here, or with the tile taken
-			// now (its successor's first tile is then requested a tile ahead, like any other tile): records and UnitAux through the
-			// scalar cache, issued before the work below and read after it.
+			// The half's next unit (PF: and the one after it), in case this call needs them -- the unit ends here, or (PF) with the tile
+			// taken now, and its successor's first tile is then requested a tile ahead: records and UnitAux through the scalar cache,
+			// issued before the work below and read after it.
 			const uint32_t nx0 = (uint32_t)c_next, ne0 = (uint32_t)((uint64_t)c_next >> 32);
 			tw_u32x4 rec0 = {0u, 0u, 0u, 0u}, aux0 = {0u, 0u, 0u, 0u}, rec1 = {0u, 0u, 0u, 0u};
 			const bool rec0_ok = nx0 < ne0 && (int64_t)nx0 < n_units;       // (whenever they are known: a unit can end before its bound says so)
-			const bool rec1_ok = rec0_ok && nx0 + 1u < ne0 && (int64_t)nx0 + 1 < n_units;
+			const bool rec1_ok = PF && rec0_ok && nx0 + 1u < ne0 && (int64_t)nx0 + 1 < n_units;
 			if (rec0_ok) { rec0 = *TW_CONST(tw_u32x4, g.units + nx0); aux0 = *TW_CONST(tw_u32x4, g.aux + nx0); }
 			if (rec1_ok) rec1 = *TW_CONST(tw_u32x4, g.units + nx0 + 1u);
 
 			// takes a tile's anchors (one per lane, raw mm128_t) into the half's LDS: where the unit ends (first gap > max_dist_x,
-			// chain.c:252), XY ring (the anchors as predecessors), XQ / SP (as the current anchor).  Returns the anchors the tile holds
+			// chain.c:252), XY ring (the anchors as predecessors and as the current anchor), SP.  Returns the anchors the tile holds
 			// (0: the unit ended exactly at its start).
 			auto take_tile = [&](const uint64_t an_x, const uint64_t an_y) -> int {
 				const int i_lane = c_tile0 + lane;
@@ -356,25 +403,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 				const uint64_t stop_m = __builtin_amdgcn_ballot_w64(stop);
 				const int cnt = stop_m ? __builtin_ctzll(stop_m) : TW_TILE;
 				c_xcarry = readlane_u64(an_x, 63);
-				u.pc = TW_SEL(hm, curb, u.pc); u.pend = TW_SEL(hm, curb + ((uint32_t)cnt << 3), u.pend);
+				if constexpr (L::HAS_XQ) { u.pc = TW_SEL(hm, curb, u.pc); u.pend = TW_SEL(hm, curb + ((uint32_t)cnt << 3), u.pend); }
+				else u.pend = TW_SEL(hm, mkb + ((uint32_t)(c_tile0 + cnt - 1) << 2), u.pend);
 				if (cnt == 0) return 0;
 				wave_mem_fence();
 				if (lane < cnt) {
 					const int sp = span_of_hi((uint32_t)(an_y >> 32));
 					tw_st64((((uint32_t)i_lane & 127u) << 4 | (uint32_t)hs << 3) + TW_XY, (uint32_t)an_x + 1u, (uint32_t)an_y + 1u);
-					tw_st64(curb + ((uint32_t)lane << 3), (uint32_t)an_x, (uint32_t)an_y);
-					tw_st8(spb + (uint32_t)lane, sp - 1);
+					if constexpr (L::HAS_XQ) {
+						tw_st64(curb + ((uint32_t)lane << 3), (uint32_t)an_x, (uint32_t)an_y);
+						tw_st8(spb + (uint32_t)lane, sp - 1);
+					} else tw_st8((((uint32_t)i_lane & 63u) << 1 | (uint32_t)hs) + L::SP, sp - 1);
 					// first_child[] starts at "none" for every anchor the kernel takes in: stored here, a whole tile of passes before the
 					// tile's flush (or any later one) lowers it with atomics -- and service() waits for the wave's outstanding memory
 					// operations when it starts, so those atomics come after this store in memory as well.  No batch-wide memset.
 					g.first_child[c_base + i_lane] = NO_CHILD;
 				}
 				wave_mem_fence();
-				// the tile after this one: the load is issued now and read at the half's next service, 64 anchors of work later
-				if (cnt == TW_TILE && c_tile0 + TW_TILE < c_room) {            // (else: the unit ends with this tile; the registers are for its successor)
-					uint64_t rx = 0, ry = 0;
-					if (i_lane + TW_TILE < c_room) { const ulonglong2 t = g.a[c_base + i_lane + TW_TILE]; rx = t.x; ry = t.y; }
-					if (hs) { nx1_x = rx; nx1_y = ry; pfu1 = -1; } else { nx0_x = rx; nx0_y = ry; pfu0 = -1; }
+				if constexpr (PF) {
+					// the tile after this one: the load is issued now and read at the half's next service, 64 anchors of work later
+					if (cnt == TW_TILE && c_tile0 + TW_TILE < c_room) {        // (else: the unit ends with this tile; the registers are for its successor)
+						uint64_t rx = 0, ry = 0;
+						if (i_lane + TW_TILE < c_room) { const ulonglong2 t = g.a[c_base + i_lane + TW_TILE]; rx = t.x; ry = t.y; }
+						if (hs) { nx1_x = rx; nx1_y = ry; pfu1 = -1; } else { nx0_x = rx; nx0_y = ry; pfu0 = -1; }
+					}
 				}
 				return cnt;
 			};
@@ -391,9 +443,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 				}
 				goes_on = false;
 			}
+			// the unit's next tile: in registers since the last service (PF), else loaded now
 			if (goes_on) {
 				c_tile0 += TW_TILE;
-				if (take_tile(hs ? nx1_x : nx0_x, hs ? nx1_y : nx0_y) == 0) goes_on = false;   // it ended exactly on the boundary
+				uint64_t nt_x = 0, nt_y = 0;
+				if constexpr (PF) { nt_x = hs ? nx1_x : nx0_x; nt_y = hs ? nx1_y : nx0_y; }
+				else if (c_tile0 + lane < c_room) { const ulonglong2 t = g.a[c_base + c_tile0 + lane]; nt_x = t.x; nt_y = t.y; }
+				if (take_tile(nt_x, nt_y) == 0) goes_on = false;     // (0: the unit ended exactly on the boundary)
 			}
 			TW_STAMP_B(if (g.stamp) st_take += (unsigned int)(TW_NOW() - th0);)
 			// ---- flush the finished tile
@@ -461,7 +517,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 				}
 				if ((int64_t)nx >= n_units) {
 					c_next = (int64_t)((uint64_t)ne << 32 | nx); live = false;
-					u.pc = TW_SEL(hm, curb, u.pc); u.pend = TW_SEL(hm, curb, u.pend);
+					if constexpr (L::HAS_XQ) { u.pc = TW_SEL(hm, curb, u.pc); u.pend = TW_SEL(hm, curb, u.pend); }
+					else u.pend = TW_SEL(hm, 0u, u.pend);
 					break;
 				}
 				TW_STAMP_C(const unsigned long long tc0 = g.stamp ? TW_NOW() : 0;)
@@ -471,21 +528,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 				c_next = (int64_t)((uint64_t)ne << 32 | (nx + 1u));
 				Unit un;
 				un.start = (int64_t)((uint64_t)rec0.y << 32 | rec0.x); un.read = (int32_t)rec0.z; un.len = (int32_t)rec0.w;
-				if (!params_ok || (aux0.z & 1u) || g.par.n_segs > 1) {         // not for this kernel: hand the unit over
+				if (!params_ok || (aux0.z & 1u) || g.par.n_segs > 1 || (ONE_LUT && cur_key_now != 0xffffffffu && aux0.y != cur_key_now)) {
+					// not for this kernel: hand the unit over (the key test, one table per wave, cannot fail: key_range)
 					if (lane == 0) g.left[atomicAdd(g.left_cnt, 1u)] = un;
 					continue;
 				}
 				c_base = un.start; c_rel0 = (int)aux0.x; c_room = un.len; c_read = un.read; c_tile0 = 0;
-				// the unit's first tile: requested a tile ago if the unit before it ended as foreseen
-				uint64_t tl_x, tl_y;
+				// the unit's first tile: (PF) requested a tile ago if the unit before it ended as foreseen, else loaded now
+				uint64_t tl_x = 0, tl_y = 0;
 				TW_STAMP_C(const unsigned long long tc1 = g.stamp ? TW_NOW() : 0;)
-				TW_STAMP_C(if (g.stamp && (hs ? pfu1 : pfu0) == (int32_t)c_base) ++st_n_unit;)
-				if ((hs ? pfu1 : pfu0) == (int32_t)c_base) { tl_x = hs ? nx1_x : nx0_x; tl_y = hs ? nx1_y : nx0_y; }
-				else {
-					tl_x = 0; tl_y = 0;
-					if (lane < c_room) { const ulonglong2 t = g.a[c_base + lane]; tl_x = t.x; tl_y = t.y; }
-				}
-				if (hs) pfu1 = -1; else pfu0 = -1;
+				TW_STAMP_C(if (g.stamp && PF && (hs ? pfu1 : pfu0) == (int32_t)c_base) ++st_n_unit;)
+				if (PF && (hs ? pfu1 : pfu0) == (int32_t)c_base) { tl_x = hs ? nx1_x : nx0_x; tl_y = hs ? nx1_y : nx0_y; }
+				else if (lane < c_room) { const ulonglong2 t = g.a[c_base + lane]; tl_x = t.x; tl_y = t.y; }
+				if constexpr (PF) { if (hs) pfu1 = -1; else pfu0 = -1; }
 				TW_STAMP_C(if (g.stamp) { asm volatile("" :: "v"(tl_x), "v"(tl_y)); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); st_take += (unsigned int)(TW_NOW() - tc1); })
 				TW_STAMP_C(const unsigned long long tc2 = g.stamp ? TW_NOW() : 0;)
 				// LDS of the half for a new unit: marks never match, every XY slot fails the window test, the read's table (as bytes) unless
@@ -499,7 +554,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 						tw_st32(lutb + ((uint32_t)k << 2), (int)w);
 					}
 					cur_key_now = aux0.y;
-					if (lane == 0) tw_st32(TW_KEY + 4u * (uint32_t)hs, (int)cur_key_now);
+					if (lane == 0) tw_st32(keya, (int)cur_key_now);
 				}
 				const uint32_t x_none = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tl_x, 0) - (uint32_t)maxx - 1u;   // "no anchor here" (x+1 encoding)
 				for (int k = lane; k < 128; k += 64) tw_st64(((uint32_t)k << 4 | (uint32_t)hs << 3) + TW_XY, x_none, 0u);
@@ -510,13 +565,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 				if (take_tile(tl_x, tl_y) > 0) goes_on = true;                 // (a unit has at least two anchors: always)
 				TW_STAMP_C(if (g.stamp) { st_tail += (unsigned int)(TW_NOW() - tc2); ++st_unit; })
 			}
-			// ---- the unit ends with the tile just taken: request its successor's first tile now, if the successor is known
-			if (live) {
-				const uint32_t cnt_now = ((uint32_t)__builtin_amdgcn_readlane((int)u.pend, 32 * hs) - curb) >> 3;
+			// ---- (PF) the unit ends with the tile just taken: request its successor's first tile now, if the successor is known
+			if (PF && live) {
+				const int cnt_now = tile_cnt();
 				const uint32_t nxn = (uint32_t)c_next, nen = (uint32_t)((uint64_t)c_next >> 32);
 				if (!(cnt_now == TW_TILE && c_tile0 + TW_TILE < c_room) && (hs ? pfu1 : pfu0) < 0 && nxn < nen && (int64_t)nxn < n_units &&
 				    ((nxn == nx0 && rec0_ok && !rec0_used) || (nxn == nx0 + 1u && rec1_ok))) {
-					const tw_u32x4 rn = nxn == nx0 ? rec0 : rec1;                // (nxn == nx0: the loop above did not run, rec0 is untouched)
+					const tw_u32x4 rn = nxn == nx0 ? rec0 : rec1;            // (nxn == nx0: the loop above did not run, rec0 is untouched)
 					const int32_t st = (int32_t)rn.x, ln = (int32_t)rn.w;
 					uint64_t rx = 0, ry = 0;
 					if (lane < ln) { const ulonglong2 t = g.a[(int64_t)st + lane]; rx = t.x; ry = t.y; }
@@ -553,7 +608,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 		if (__builtin_amdgcn_inverse_ballot_w64(D)) {
 			u.m4 += 4u;
 			u.S = ((u.m4 - c_mkbase) << 2) | c_8h;
-			u.pc += 8u;
+			if constexpr (L::HAS_XQ) u.pc += 8u;
 		} else {
 			if (hl == 0) {                                                   // what the second chunk starts from
 				tw_st64(st_addr + TW_CARRY, cur.x, cur.y);
@@ -572,7 +627,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 					g.left[atomicAdd(g.left_cnt, 1u)] = un;                  // k_chain_units goes on from the tile this scan is in (the tiles
 					                                                         // before it are flushed).  The unit is over for this kernel: an empty tile ...
 				}
-				u.pc = curbase; u.pend = curbase;                            // ... has nothing to flush and cannot go on: service() picks the half's next unit
+				u.pc = curbase; u.pend = L::HAS_XQ ? curbase : 0u;            // ... has nothing to flush and cannot go on: service() picks the half's next unit
 			}
 			return giveup;
 		}
@@ -595,12 +650,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 			uint32_t a_cur;
 			for (;;) {
 				const uint32_t t0 = u.S - L16;                               // lane k <-> predecessor j = jtop - k of its half's anchor
+				const uint32_t S1 = u.S + 16u;                               // 16 i + 8h
 				const tw_u32x2 xy = tw_ld64((t0 & 0x7f8u) + TW_XY);
+				// the anchor itself: one table, from its XY slot (x + 1, q + 1); two tables, from XQ (x, q)
+				const tw_u32x2 cur = tw_ld64(L::HAS_XQ ? u.pc : (S1 & 0x7f8u) + TW_XY);
+#if defined(__HIP_DEVICE_COMPILE__)
+				__builtin_amdgcn_sched_barrier(0);                           // the differences wait for these two reads only, not for PF's
+#endif
 				const tw_u32x2 pf = tw_ld64((t0 & 0x3f8u) + TW_PF);
-				const tw_u32x2 cur = tw_ld64(u.pc);                          // the anchor itself: x, q
-				const int spm1 = tw_ld_u8((u.pc >> 3) + TW_SP_OF_XQ);        // ... and q_span - 1
-				const uint32_t drm1 = cur.x - xy.x, dqm1 = cur.y - xy.y;     // the ring holds x + 1, q + 1: differences minus one
-				const uint32_t ddl = tw_sad(drm1, dqm1, c_lut);              // |dr - dq| + the half's table base
+				const int spm1 = tw_ld_u8(L::HAS_XQ ? (u.pc >> 3) + L::SP_OF_XQ : __builtin_amdgcn_ubfe(S1, 3, 7) + L::SP);   // ... and q_span - 1
+				// differences minus one (the ring holds x + 1, q + 1)
+				const uint32_t drm1 = L::HAS_XQ ? cur.x - xy.x : tw_sub_m1(cur.x, xy.x), dqm1 = L::HAS_XQ ? cur.y - xy.y : tw_sub_m1(cur.y, xy.y);
+				const uint32_t ddl = ONE_LUT ? tw_absdiff(drm1, dqm1) : tw_sad(drm1, dqm1, c_lut);   // |dr - dq| + the half's table base
 				const uint32_t dqs = SAMEGAP ? dqm1 : __builtin_elementwise_add_sat(dqm1, c_dqoff);
 				const uint32_t m3 = max(max(drm1, dqs), ddl + c_cbwl);
 				const uint64_t okm = TW_ULT(m3, c_M);                        // chain.c:252-260 as one compare
@@ -610,7 +671,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 				tw_st32(dst, (int)u.m4);
 				wave_mem_fence();
 				const int tj = tw_ld32(c_own);
-				const int lutv = tw_ld_i8(min(ddl, c_bwl));
+				const int lutv = tw_ld_i8(min(ddl, c_bwl) + LUT_OFF);
 #if defined(__HIP_DEVICE_COMPILE__)
 				__builtin_amdgcn_sched_barrier(0);
 #endif
@@ -628,7 +689,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 				if (__builtin_expect((TW_SGT(cB, 0) & A) != 0, 0)) { force_general = true; break; }
 				// the running max goes to PF[i]: the half's last A lane writes its own score and predecessor, or (none) the half's
 				// lane 0 writes "no predecessor, q_span" (minus one)
-				const uint32_t S1 = u.S + 16u;
 				a_cur = S1 & 0x3f8u;                                         // PF slot of anchor i (S = 16 (i - 1) + 8h in the first chunk)
 				{
 					const uint32_t wp = TW_SEL(A, u.m4 - c_own, 0xfffffffcu);      // 4 j of the lane's predecessor: 4 (i - 1 - k)
@@ -639,8 +699,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 				X = (TW_SGE(cB, c_ms) & B) | OUT;
 				if (__builtin_expect(tw_both_halves(X) == 0, 0)) break;
 				u.m4 += 4u; u.S = S1;
-				u.pc += 8u;
-				tile = TW_SGE(u.pc, u.pend);
+				if constexpr (L::HAS_XQ) { u.pc += 8u; tile = TW_SGE(u.pc, u.pend); }
+				else tile = TW_SGE(u.m4, u.pend);
 				TW_STAMP(if (g.stamp) ++st_n_fast;)
 				if (__builtin_expect(tile != 0, 0)) break;
 				wave_mem_fence();
@@ -653,24 +713,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 			// ------------------------------------------------------------ general pass: second chunks, idle halves, interleaved walks
 			force_general = false;
 			const uint32_t t0 = u.S - L16;
+			const uint32_t xcur = ((((u.m4 - c_mkbase) + 4u) << 2) & 0x7f8u) | c_8h;   // XY slot of anchor i (m4 = 4 (i - 1) + mark base)
 			const tw_u32x2 xy = tw_ld64((t0 & 0x7f8u) + TW_XY);
 			const tw_u32x2 pf = tw_ld64((t0 & 0x3f8u) + TW_PF);
-			const tw_u32x2 cur = tw_ld64(u.pc);
-			const int spm1 = tw_ld_u8((u.pc >> 3) + TW_SP_OF_XQ);
+			const tw_u32x2 cur = tw_ld64(L::HAS_XQ ? u.pc : xcur + TW_XY);
+			const int spm1 = tw_ld_u8(L::HAS_XQ ? (u.pc >> 3) + L::SP_OF_XQ : ((xcur >> 3) & 0x7fu) + L::SP);
 			const uint64_t first = ~contm;                                       // halves in their first chunk: running max = q_span, nothing carried
 			const tw_u32x2 carry = tw_ld64(st_addr + TW_CARRY);
 			const int maxf = TW_SEL(first, spm1, (int)carry.y);
 			const uint32_t maxj4 = TW_SEL(first, 0xfffffffcu, carry.x);
 			const int nskip0 = TW_SEL(first, 0, tw_ld32(st_addr + TW_CARRY + 8u));
 			const uint32_t kb4 = TW_SEL(first, 0u, 128u);                        // 128 * c
-			const uint32_t drm1 = cur.x - xy.x, dqm1 = cur.y - xy.y;
-			const uint32_t ddl = tw_sad(drm1, dqm1, c_lut);
+			const uint32_t drm1 = L::HAS_XQ ? cur.x - xy.x : tw_sub_m1(cur.x, xy.x), dqm1 = L::HAS_XQ ? cur.y - xy.y : tw_sub_m1(cur.y, xy.y);
+			const uint32_t ddl = ONE_LUT ? tw_absdiff(drm1, dqm1) : tw_sad(drm1, dqm1, c_lut);
 			const uint32_t dqs = SAMEGAP ? dqm1 : __builtin_elementwise_add_sat(dqm1, c_dqoff);
 			const uint32_t m3 = max(max(drm1, dqs), ddl + c_cbwl);
 			// not evaluated: lane 31 of a second chunk (j = i - 64 shares its PF slot with anchor i itself) and idle halves
 			const uint64_t okm = TW_ULT(m3, c_M) & ~(contm & TW_HI31) & live_m;
 			const int sc0 = min(min((int)dqm1, (int)drm1), spm1);
-			const int lutv = tw_ld_i8(min(ddl, c_bwl));
+			const int lutv = tw_ld_i8(min(ddl, c_bwl) + LUT_OFF);
 			const uint32_t dst = TW_SEL(okm, min(u.m4 - pf.x, c_far), c_far);
 			tw_st32(dst, (int)u.m4);
 			wave_mem_fence();
@@ -696,7 +757,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 				brk = TW_SGT(nskip_after, c_ms) & B;
 				Ap = tw_below_first(A, brk);
 			}
-			const uint32_t a_cur = (((((u.m4 - c_mkbase) + 4u) << 2) & 0x3f8u) | c_8h) + TW_PF;   // PF slot of anchor i (m4 = 4 (i - 1) + mark base)
+			const uint32_t a_cur = (xcur & 0x3f8u) + TW_PF;                      // PF slot of anchor i
 			{
 				const uint32_t wp = TW_SEL(Ap, u.m4 - c_own - kb4, maxj4);          // 4 j = 4 (i - 1 - 32 c - k)
 				const int wf = TW_SEL(Ap, sc, maxf);
@@ -706,7 +767,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 			svc = slow_tail(D, a_cur, nskip_after);
 		}
 		// ---------------------------------------------------------------- tile exhausted (or unit handed over): flush, next tile / unit
-		svc |= tw_smear_halves(TW_SGE(u.pc, u.pend) & live_m & ~contm);
+		svc |= tw_smear_halves((L::HAS_XQ ? TW_SGE(u.pc, u.pend) : TW_SGE(u.m4, u.pend)) & live_m & ~contm);
 		if (__builtin_expect(svc != 0, 0)) {
 			TW_STAMP(const unsigned long long ts = g.stamp ? TW_NOW() : 0;)
 			service(svc & live_m);
@@ -720,34 +781,35 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 #undef TW_COLD
 }
 
-size_t twin_lds_bytes() { return TW_LDS_BYTES; }
+size_t twin_lds_bytes(bool one_table) { return one_table ? TwLayout<true>::BYTES : TwLayout<false>::BYTES; }
 
-hipError_t launch_chain_twin(hipStream_t st, const Params &par, int64_t max_units, const int64_t *d_off, const void *d_a,
-                             const unsigned long long *d_sumq, const uint16_t *d_lut, int lut_stride, const Unit *d_units,
-                             const unsigned long long *d_counters, int32_t *d_f, int32_t *d_p, int32_t *d_v,
-                             int32_t *d_first_child, uint8_t *d_flags, Unit *d_left, unsigned int *d_left_cnt, int force_left, int64_t total,
-                             const UnitAux *d_unit_aux, const unsigned int *d_route, unsigned int *d_queue)
+// workgroups per CU a launch asks for at most: what the LDS allows (32 with one table, 24 with two) and the registers (TwWaves)
+int twin_max_wg_per_cu(bool samegap, bool one_table)
 {
-	if (max_units <= 0) return hipSuccess;
-	if (!d_unit_aux) return hipErrorInvalidValue;
-	// persistent waves: as many as the chip holds at the kernel's occupancy (6 per SIMD), each half taking units from a queue
-	int dev = 0, cus = 256;
-	if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+	const int lds_wg = one_table ? 32 : 24;                          // 5120 / 6400 bytes of LDS allocated per workgroup (4864 / 6400 used)
+	const int waves = one_table ? (samegap ? TwWaves<true, true>::N : TwWaves<false, true>::N)
+	                            : (samegap ? TwWaves<true, false>::N : TwWaves<false, false>::N);
+	return 4 * waves < lds_wg ? 4 * waves : lds_wg;
+}
+
+// one launch of the layout ONE_LUT (the kernel returns at once when the batch is not for it)
+template <bool ONE_LUT>
+static hipError_t launch_twin_layout(hipStream_t st, TwinArgs g, int64_t max_units, int cus, unsigned int *d_queue)
+{
+	// persistent waves: as many as the chip holds at the layout's occupancy (LDS, and TwWaves per SIMD for the registers), each half
+	// taking units from a queue.  CHAINDP_TWIN_WG_PER_CU lowers it (tuning).
+	const bool samegap = g.par.max_dist_y >= g.par.max_dist_x;
+	const int max_wg = twin_max_wg_per_cu(samegap, ONE_LUT);
 	int64_t blocks = (max_units + 2 * TW_QCH - 1) / (2 * TW_QCH);
-	static const int wg_per_cu = getenv("CHAINDP_TWIN_WG_PER_CU") ? atoi(getenv("CHAINDP_TWIN_WG_PER_CU")) : 24;   // (tuning: read once)
-	const int64_t cap = (int64_t)cus * (wg_per_cu >= 1 && wg_per_cu <= 24 ? wg_per_cu : 24);
+	static const int wg_env = getenv("CHAINDP_TWIN_WG_PER_CU") ? atoi(getenv("CHAINDP_TWIN_WG_PER_CU")) : 0;   // (tuning: read once)
+	const int64_t cap = (int64_t)cus * (wg_env >= 1 && wg_env <= max_wg ? wg_env : max_wg);
 	if (blocks > cap) blocks = cap;
 	if (blocks < 1) blocks = 1;
 	blocks = (blocks + 7) & ~(int64_t)7;                           // eight grab counters, workgroup b on counter b mod 8: the same number of halves on each
-	if (!d_queue) return hipErrorInvalidValue;
 	{
 		const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)d_queue, (int)(2 * blocks / 8), 8 * 64, st);   // every counter starts behind its halves' first grabs
 		if (e != hipSuccess) return e;
 	}
-	TwinArgs g;
-	g.par = par; g.off = d_off; g.a = (const ulonglong2*)d_a; g.sumq = d_sumq; g.lut = d_lut; g.lut_stride = lut_stride;
-	g.units = d_units; g.aux = d_unit_aux; g.counters = d_counters; g.f = d_f; g.p = d_p; g.v = d_v; g.first_child = d_first_child; g.flags = d_flags;
-	g.left = d_left; g.left_cnt = d_left_cnt; g.queue = d_queue; g.route = d_route; g.force_left = force_left; g.total = total;
 	// diagnostic: CHAINDP_TWIN_STAMP=1 makes the kernel stamp where its waves' time goes (s_memtime: shader-clock ticks) and this
 	// function print the averages -- it synchronises, so never set it in a timed run
 	static unsigned long long *d_stamp = nullptr;
@@ -757,13 +819,13 @@ hipError_t launch_chain_twin(hipStream_t st, const Params &par, int64_t max_unit
 	if (g.stamp) (void)hipMemsetAsync(d_stamp, 0, (size_t)blocks * 96, st);
 	{
 		hipFuncAttributes fa;                                        // LDS is addressed by raw byte offsets from 0: no static LDS may sit in front
-		const void *fn = par.max_dist_y >= par.max_dist_x ? (const void*)k_chain_twin<true> : (const void*)k_chain_twin<false>;
+		const void *fn = samegap ? (const void*)k_chain_twin<true, ONE_LUT> : (const void*)k_chain_twin<false, ONE_LUT>;
 		const hipError_t e = hipFuncGetAttributes(&fa, fn);
 		if (e != hipSuccess) return e;
 		if (fa.sharedSizeBytes != 0) return hipErrorInvalidConfiguration;
 	}
-	if (par.max_dist_y >= par.max_dist_x) hipLaunchKernelGGL(k_chain_twin<true>, dim3((unsigned)blocks), dim3(64), TW_LDS_BYTES, st, g);
-	else hipLaunchKernelGGL(k_chain_twin<false>, dim3((unsigned)blocks), dim3(64), TW_LDS_BYTES, st, g);
+	if (samegap) hipLaunchKernelGGL((k_chain_twin<true, ONE_LUT>), dim3((unsigned)blocks), dim3(64), TwLayout<ONE_LUT>::BYTES, st, g);
+	else hipLaunchKernelGGL((k_chain_twin<false, ONE_LUT>), dim3((unsigned)blocks), dim3(64), TwLayout<ONE_LUT>::BYTES, st, g);
 	if (g.stamp) {
 		std::vector<unsigned long long> hb((size_t)blocks * 12);
 		if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(hb.data(), d_stamp, hb.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
@@ -772,14 +834,35 @@ hipError_t launch_chain_twin(hipStream_t st, const Params &par, int64_t max_unit
 				const unsigned long long *o = &hb[(size_t)b * 12];
 				tot += o[0]; svc += o[1]; flush += o[2]; unit += o[3]; nsvc += o[4]; nfast += o[5]; nunit += o[6]; head += o[8]; take += o[9]; tail += o[10]; ++nb;
 			}
-			fprintf(stderr, "[twin stamp raw] sums over waves: head %.0f take %.0f tail %.0f unit %.0f n_unit %.0f (build 3: ticks until the record / the first tile / the rest of a unit switch; switches; first tiles requested ahead)\n", head, take, tail, unit, nunit);
-			fprintf(stderr, "[twin stamp] %.0f waves, %.0f ticks each: service %.1f%% (%.0f calls, %.0f ticks each: cold state and decisions %.0f, next tile %.0f, flush %.0f, "
+			if (nb > 0) fprintf(stderr, "[twin stamp raw] sums over waves: head %.0f take %.0f tail %.0f unit %.0f n_unit %.0f (build 3: ticks until the record / the first tile / the rest of a unit switch; switches; first tiles requested ahead)\n", head, take, tail, unit, nunit);
+			if (nb > 0) fprintf(stderr, "[twin stamp] %.0f waves, %.0f ticks each: service %.1f%% (%.0f calls, %.0f ticks each: cold state and decisions %.0f, next tile %.0f, flush %.0f, "
 			                "unit switch %.0f (%.0f switches, %.0f ticks each), first anchor and cold state back %.0f), passes %.0f (%.0f ticks each, everything else included)\n",
 			        nb, tot / nb, 100.0 * svc / tot, nsvc, svc / (nsvc > 0 ? nsvc : 1), head / (nsvc > 0 ? nsvc : 1), take / (nsvc > 0 ? nsvc : 1), flush / (nsvc > 0 ? nsvc : 1),
 			        unit / (nsvc > 0 ? nsvc : 1), nunit, unit / (nunit > 0 ? nunit : 1), tail / (nsvc > 0 ? nsvc : 1), nfast, (tot - svc) / (nfast > 0 ? nfast : 1));
 		}
 	}
 	return hipGetLastError();
+}
+
+hipError_t launch_chain_twin(hipStream_t st, const Params &par, int64_t max_units, const int64_t *d_off, const void *d_a,
+                             const unsigned long long *d_sumq, const uint16_t *d_lut, int lut_stride, const Unit *d_units,
+                             const unsigned long long *d_counters, int32_t *d_f, int32_t *d_p, int32_t *d_v,
+                             int32_t *d_first_child, uint8_t *d_flags, Unit *d_left, unsigned int *d_left_cnt, int force_left, int64_t total,
+                             const UnitAux *d_unit_aux, const unsigned int *d_key_range, unsigned int *d_route, unsigned int *d_queue, int two_tables)
+{
+	if (max_units <= 0) return hipSuccess;
+	if (!d_unit_aux || !d_key_range || !d_route || !d_queue) return hipErrorInvalidValue;
+	int dev = 0, cus = 256;
+	if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+	TwinArgs g;
+	g.par = par; g.off = d_off; g.a = (const ulonglong2*)d_a; g.sumq = d_sumq; g.lut = d_lut; g.lut_stride = lut_stride;
+	g.units = d_units; g.aux = d_unit_aux; g.counters = d_counters; g.f = d_f; g.p = d_p; g.v = d_v; g.first_child = d_first_child; g.flags = d_flags;
+	g.left = d_left; g.left_cnt = d_left_cnt; g.queue = d_queue; g.key_range = d_key_range; g.route = d_route; g.two_tables = two_tables != 0;
+	g.force_left = force_left; g.total = total; g.stamp = nullptr;
+	// both layouts, one table first: the device decides which one takes the batch (g.route), the other returns at once
+	hipError_t e = launch_twin_layout<true>(st, g, max_units, cus, d_queue);
+	if (e == hipSuccess) e = launch_twin_layout<false>(st, g, max_units, cus, d_queue);
+	return e;
 }
 
 } // namespace chaindp
