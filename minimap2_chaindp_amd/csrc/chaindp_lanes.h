@@ -41,6 +41,14 @@ __device__ __forceinline__ void tw_st128(uint32_t a, uint32_t x, uint32_t y, uin
 #define TW_VREG(x) ((void)(x))
 #endif
 
+// hides how a vector value was computed, so that the compiler does not fold what follows into a three-operand instruction (which
+// issues at half rate); unlike TW_VREG it does not pin the value's place in the schedule
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TW_OPAQUE(x) asm("" : "+v"(x))
+#else
+#define TW_OPAQUE(x) ((void)(x))
+#endif
+
 // a lane mask is wave-uniform by construction; where the compiler's divergence analysis loses track of that (values merged
 // behind loops) this keeps it in scalar registers (folds away when it already is)
 #define TW_UNI(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))

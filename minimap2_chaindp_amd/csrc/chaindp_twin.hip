@@ -50,7 +50,7 @@
 namespace chaindp {
 
 #define TW_XY 0u
-#define TW_PF 2048u
+#define TW_PF 2048u                     // (tw_st64_pf_lanes has it as the DS offset: static_assert there)
 #define TW_V 3072u
 #define TW_LUT_BYTES 512u                // one table (bw + 1 <= 512 entries)
 #define TW_ST_HALF 56u
@@ -165,6 +165,31 @@ __device__ __forceinline__ uint64_t tw_below_first(uint64_t m, uint64_t b)
 
 #define TW_HI31 0x8000000080000000ull
 
+// per half: the bits of a above the lowest set bit of b, for disjoint a and b (b's lowest bit and all above it are set in -b; none
+// where b has no bit)
+__device__ __forceinline__ uint64_t tw_above_first(uint64_t a, uint64_t b)
+{
+	uint32_t lo = 0, hi = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+	asm("s_sub_i32 %0, 0, %2\n\ts_sub_i32 %1, 0, %3" : "=&s"(lo), "=&s"(hi) : "s"(TW_UNI((uint32_t)b)), "s"(TW_UNI((uint32_t)(b >> 32))) : "scc");
+#endif
+	return a & ((uint64_t)hi << 32 | lo);
+}
+
+// ds_write_b64 of (x, y) to the PF ring (byte a + TW_PF) by the lanes of m alone, exec set by hand: as a branch on m it would be the one
+// divergent branch of the fast loop, and the compiler's structurizer would then merge the loop's uniform exits into flag registers
+__device__ __forceinline__ void tw_st64_pf_lanes(uint64_t m, uint32_t a, uint32_t x, uint32_t y)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	tw_u32x2 t; t.x = x; t.y = y;
+	uint64_t saved;
+	asm volatile("s_and_saveexec_b64 %0, %1\n\tds_write_b64 %2, %3 offset:2048\n\ts_mov_b64 exec, %0"
+	             : "=&s"(saved) : "s"(m), "v"(a), "v"(t) : "memory", "scc");
+#endif
+}
+static_assert(TW_PF == 2048u, "tw_st64_pf_lanes writes the PF ring at DS offset 2048");
+
+
 struct TwinArgs {
 	Params par;
 	const int64_t *off;
@@ -249,7 +274,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 	const int h = lane >> 5, hl = lane & 31;
 
 	// ---- per-lane constants (vector registers on purpose, see TW_VREG)
-	uint32_t L16 = (uint32_t)hl << 4;
+	uint32_t L16 = ((uint32_t)hl + 1u) << 4;                        // 16 (k + 1): lane k's predecessor is anchor i - 1 - k
 	const uint32_t mkbase = L::MK + TW_MK_HALF * (uint32_t)h;      // this half's mark words
 	const uint32_t curbase = L::XQ + L::XQ_HALF * (uint32_t)h;     // (two tables) this half's XQ entries
 	uint32_t c_mkbase = mkbase;
@@ -645,74 +670,157 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 			// ------------------------------------------------------------ both halves in their first chunk (n_skip = 0, max_j = none).
 			// A loop of its own: while both halves finish every scan in the first chunk nothing but the pass below runs, and its
 			// state is updated in place.
-			uint64_t B, X, tile;
-			int cB;
-			uint32_t a_cur;
-			for (;;) {
-				const uint32_t t0 = u.S - L16;                               // lane k <-> predecessor j = jtop - k of its half's anchor
-				const uint32_t S1 = u.S + 16u;                               // 16 i + 8h
-				const tw_u32x2 xy = tw_ld64((t0 & 0x7f8u) + TW_XY);
-				// the anchor itself: one table, from its XY slot (x + 1, q + 1); two tables, from XQ (x, q)
-				const tw_u32x2 cur = tw_ld64(L::HAS_XQ ? u.pc : (S1 & 0x7f8u) + TW_XY);
-#if defined(__HIP_DEVICE_COMPILE__)
-				__builtin_amdgcn_sched_barrier(0);                           // the differences wait for these two reads only, not for PF's
-#endif
-				const tw_u32x2 pf = tw_ld64((t0 & 0x3f8u) + TW_PF);
-				const int spm1 = tw_ld_u8(L::HAS_XQ ? (u.pc >> 3) + L::SP_OF_XQ : __builtin_amdgcn_ubfe(S1, 3, 7) + L::SP);   // ... and q_span - 1
-				// differences minus one (the ring holds x + 1, q + 1)
-				const uint32_t drm1 = L::HAS_XQ ? cur.x - xy.x : tw_sub_m1(cur.x, xy.x), dqm1 = L::HAS_XQ ? cur.y - xy.y : tw_sub_m1(cur.y, xy.y);
-				const uint32_t ddl = ONE_LUT ? tw_absdiff(drm1, dqm1) : tw_sad(drm1, dqm1, c_lut);   // |dr - dq| + the half's table base
-				const uint32_t dqs = SAMEGAP ? dqm1 : __builtin_elementwise_add_sat(dqm1, c_dqoff);
-				const uint32_t m3 = max(max(drm1, dqs), ddl + c_cbwl);
-				const uint64_t okm = TW_ULT(m3, c_M);                        // chain.c:252-260 as one compare
-				// the mark round trip (chain.c:281: store by distance, the others to the sink; then the lane's own word) and the table
-				// lookup are issued back to back, before anything waits for either
-				const uint32_t dst = TW_SEL(okm, min(u.m4 - pf.x, c_far), c_far);
-				tw_st32(dst, (int)u.m4);
-				wave_mem_fence();
-				const int tj = tw_ld32(c_own);
-				const int lutv = tw_ld_i8(min(ddl, c_bwl) + LUT_OFF);
-#if defined(__HIP_DEVICE_COMPILE__)
-				__builtin_amdgcn_sched_barrier(0);
-#endif
-				const int sc0 = min(min((int)dqm1, (int)drm1), spm1);        // chain.c:262-263, minus one
-				const int sc = TW_SEL(okm, sc0 + (int)pf.y + lutv, c_min);   // chain.c:272-273 via the table, minus one (the ring holds f - 1)
-				const int excl = max(tw_excl_max32(sc), spm1);               // (q_span - 1 >= 0: the scan's zero fill stays below it)
-				const uint64_t A = TW_SGT(sc, excl);                         // new running max (chain.c:274); masked lanes hold INT_MIN
-				B = TW_EQ(tj, u.m4) & okm & ~A;                              // marked and not better (chain.c:277)
-				const uint64_t OUT = TW_SGE(drm1, c_Mout);                   // the half's last lane is outside the window (or no anchor there yet)
-				cB = tw_below_in_half(B, hi_half);
-				// n_skip walk (chain.c:276,278) from n_skip = 0.  When every A lane of a half precedes every B lane of it, n_skip at a
-				// B lane is the number of B lanes up to it: the break is the (max_skip + 1)-th of them.  An A lane above a B lane
-				// (interleaved, rare) leaves this loop for the general pass, which redoes the anchor.
-				tile = 0; X = 0; a_cur = 0;
-				if (__builtin_expect((TW_SGT(cB, 0) & A) != 0, 0)) { force_general = true; break; }
-				// the running max goes to PF[i]: the half's last A lane writes its own score and predecessor, or (none) the half's
-				// lane 0 writes "no predecessor, q_span" (minus one)
-				a_cur = S1 & 0x3f8u;                                         // PF slot of anchor i (S = 16 (i - 1) + 8h in the first chunk)
-				{
-					const uint32_t wp = TW_SEL(A, u.m4 - c_own, 0xfffffffcu);      // 4 j of the lane's predecessor: 4 (i - 1 - k)
-					const int wf = TW_SEL(A, sc, spm1);
-					if (__builtin_amdgcn_inverse_ballot_w64(tw_last_or_lane0(A))) tw_st64(a_cur + TW_PF, wp, (uint32_t)wf);
+			if constexpr (ONE_LUT) {
+				// Inside this loop u.S runs one anchor ahead (16 i + 8h: the S1 of the pass), so that it is updated in place; every exit
+				// puts it back.  Both halves advance one anchor per pass, so the tile test is a scalar count of the passes until either
+				// half's tile ends (at least one: the test behind every pass left both halves with anchors).
+				uint64_t B, D = 0;
+				bool tile_end = false;
+				int npass = 1;
+				if constexpr (L::HAS_XQ) {
+					const int n0 = (int)(TW_UNI(__builtin_amdgcn_readlane((int)u.pend, 0)) - TW_UNI(__builtin_amdgcn_readlane((int)u.pc, 0))) >> 3;
+					const int n1 = (int)(TW_UNI(__builtin_amdgcn_readlane((int)u.pend, 32)) - TW_UNI(__builtin_amdgcn_readlane((int)u.pc, 32))) >> 3;
+					npass = max(min(n0, n1), 1);
+				} else {
+					const int n0 = (int)(TW_UNI(__builtin_amdgcn_readlane((int)u.pend, 0)) - TW_UNI(__builtin_amdgcn_readlane((int)u.m4, 0))) >> 2;
+					const int n1 = (int)(TW_UNI(__builtin_amdgcn_readlane((int)u.pend, 32)) - TW_UNI(__builtin_amdgcn_readlane((int)u.m4, 32))) >> 2;
+					npass = max(min(n0, n1), 1);
 				}
-				// scan complete: break taken, or the half's last lane is outside the window (x is sorted: nothing older can matter)
-				X = (TW_SGE(cB, c_ms) & B) | OUT;
-				if (__builtin_expect(tw_both_halves(X) == 0, 0)) break;
-				u.m4 += 4u; u.S = S1;
-				if constexpr (L::HAS_XQ) { u.pc += 8u; tile = TW_SGE(u.pc, u.pend); }
-				else tile = TW_SGE(u.m4, u.pend);
-				TW_STAMP(if (g.stamp) ++st_n_fast;)
-				if (__builtin_expect(tile != 0, 0)) break;
-				wave_mem_fence();
-			}
-			if (!force_general && tile == 0) {
-				// a half wants its second chunk.  n_skip after the first: #B, as no A lane follows a B lane
-				svc = slow_tail(tw_smear_halves(X), a_cur + TW_PF, cB + (int)__builtin_amdgcn_inverse_ballot_w64(B));
+				const uint32_t ms0 = (uint32_t)max(g.par.max_skip, 0);           // a half's scan breaks in this chunk iff it has more B lanes
+				u.S += 16u;
+				for (;;) {
+					const uint32_t S1 = u.S;                                     // 16 i + 8h
+					const uint32_t t0 = S1 - L16;                                // lane k <-> predecessor j = i - 1 - k of its half's anchor
+					const tw_u32x2 xy = tw_ld64((t0 & 0x7f8u) + TW_XY);
+					// the anchor itself: one table, from its XY slot (x + 1, q + 1); two tables, from XQ (x, q)
+					const tw_u32x2 cur = tw_ld64(L::HAS_XQ ? u.pc : (S1 & 0x7f8u) + TW_XY);
+	#if defined(__HIP_DEVICE_COMPILE__)
+					__builtin_amdgcn_sched_barrier(0);                           // the differences wait for these two reads only, not for PF's
+	#endif
+					const tw_u32x2 pf = tw_ld64((t0 & 0x3f8u) + TW_PF);
+					uint32_t a_cur = S1 & 0x3f8u;                                // PF slot of anchor i; one table: its SP byte is this / 8 (a shift:
+					TW_OPAQUE(a_cur);                                            // the compiler would make it a three-operand v_bfe from S1)
+					const int spm1 = tw_ld_u8(L::HAS_XQ ? (u.pc >> 3) + L::SP_OF_XQ : (a_cur >> 3) + L::SP);   // ... and q_span - 1
+	#ifdef TW_EXP_PAD
+					// experiment: TW_EXP_PAD dependence-free half-rate VALU instructions (three sources; the result is dropped)
+					for (int k = 0; k < TW_EXP_PAD; ++k) { uint32_t pad; asm volatile("v_max3_u32 %0, %1, %1, %1" : "=v"(pad) : "v"(c_far)); }
+	#endif
+					// differences minus one (the ring holds x + 1, q + 1)
+					const uint32_t drm1 = L::HAS_XQ ? cur.x - xy.x : tw_sub_m1(cur.x, xy.x), dqm1 = L::HAS_XQ ? cur.y - xy.y : tw_sub_m1(cur.y, xy.y);
+					const uint32_t ddl = ONE_LUT ? tw_absdiff(drm1, dqm1) : tw_sad(drm1, dqm1, c_lut);   // |dr - dq| + the half's table base
+					const uint32_t dqs = SAMEGAP ? dqm1 : __builtin_elementwise_add_sat(dqm1, c_dqoff);
+					const uint32_t m3 = max(max(drm1, dqs), ddl + c_cbwl);
+					const uint64_t okm = TW_ULT(m3, c_M);                        // chain.c:252-260 as one compare
+					// the mark round trip (chain.c:281: store by distance, the others to the sink; then the lane's own word) and the table
+					// lookup are issued back to back, before anything waits for either
+					const uint32_t dst = TW_SEL(okm, min(u.m4 - pf.x, c_far), c_far);
+					tw_st32(dst, (int)u.m4);
+					wave_mem_fence();
+					const int tj = tw_ld32(c_own);
+					const int lutv = tw_ld_i8(min(ddl, c_bwl) + LUT_OFF);
+	#if defined(__HIP_DEVICE_COMPILE__)
+					__builtin_amdgcn_sched_barrier(0);
+	#endif
+					const int sc0 = min(min((int)dqm1, (int)drm1), spm1);        // chain.c:262-263, minus one
+					const int sc = TW_SEL(okm, sc0 + (int)pf.y + lutv, c_min);   // chain.c:272-273 via the table, minus one (the ring holds f - 1)
+					const int excl = max(tw_excl_max32(sc), spm1);               // (q_span - 1 >= 0: the scan's zero fill stays below it)
+					const uint64_t A = TW_SGT(sc, excl);                         // new running max (chain.c:274); masked lanes hold INT_MIN
+					B = TW_EQ(tj, u.m4) & okm & ~A;                              // marked and not better (chain.c:277)
+					// n_skip walk (chain.c:276,278) from n_skip = 0.  When every A lane of a half precedes every B lane of it, n_skip at a
+					// B lane is the number of B lanes up to it: the break is the (max_skip + 1)-th of them.  An A lane above a B lane
+					// (interleaved, rare) leaves this loop for the general pass, which redoes the anchor.  Both tests are on the scalar side:
+					// interleaved iff a half has an A lane above its lowest B lane, and a half breaks iff it has more than max_skip B lanes.
+					const uint32_t blo = (uint32_t)B, bhi = (uint32_t)(B >> 32);
+					if (__builtin_expect(tw_above_first(A, B) != 0, 0)) { force_general = true; break; }
+					// the running max goes to PF[i]: the half's last A lane writes its own score and predecessor, or (none) the half's
+					// lane 0 writes "no predecessor, q_span" (minus one).  f is max(excl, sc) either way: sc > excl at an A lane, and at lane 0
+					// of a half without one, sc <= excl = q_span - 1
+					{
+						const uint32_t wp = TW_SEL(A, u.m4 - c_own, 0xfffffffcu);      // 4 j of the lane's predecessor: 4 (i - 1 - k)
+						const int wf = max(excl, sc);
+						tw_st64_pf_lanes(tw_last_or_lane0(A), a_cur, wp, (uint32_t)wf);
+					}
+					// scan complete: break taken, or the half's last lane is outside the window (x is sorted: nothing older can matter).
+					// The window test only matters for a half that does not break, so it waits behind the count.
+					const uint32_t nlo = (uint32_t)__builtin_popcount(blo), nhi = (uint32_t)__builtin_popcount(bhi);
+					if (__builtin_expect(min(nlo, nhi) <= ms0, 0)) {
+						const uint64_t OUT = TW_SGE(drm1, c_Mout);               // the half's last lane is outside the window (or no anchor there yet)
+						D = tw_smear_halves(OUT | (nlo > ms0 ? 0x00000000ffffffffull : 0ull) | (nhi > ms0 ? 0xffffffff00000000ull : 0ull));
+						if (__builtin_expect(tw_both_halves(D) == 0, 0)) break;
+					}
+					u.m4 += 4u; u.S += 16u;
+					if constexpr (L::HAS_XQ) u.pc += 8u;
+					TW_STAMP(if (g.stamp) ++st_n_fast;)
+					if (__builtin_expect(--npass <= 0, 0)) { tile_end = true; break; }
+					wave_mem_fence();
+				}
+				const uint32_t a_cur = u.S & 0x3f8u;                             // PF slot of the anchor the loop stopped at (no tile end)
+				u.S -= 16u;
+				if (!force_general && !tile_end) {
+					// a half wants its second chunk.  n_skip after the first: #B, as no A lane follows a B lane
+					svc = slow_tail(D, a_cur + TW_PF, tw_below_in_half(B, hi_half) + (int)__builtin_amdgcn_inverse_ballot_w64(B));
+				}
+			} else {
+				// The two-table layout keeps the pass as it was before the one-table diet: at six waves per SIMD with its tile prefetch, the
+				// diet's scalar instructions cost it more than its vector ones save (mixed-key job, chain DP +2 %).
+				uint64_t B, X, tile;
+				int cB;
+				uint32_t a_cur;
+				for (;;) {
+					const uint32_t S1 = u.S + 16u;                               // 16 i + 8h
+					const uint32_t t0 = S1 - L16;                                // lane k <-> predecessor j = jtop - k of its half's anchor
+					const tw_u32x2 xy = tw_ld64((t0 & 0x7f8u) + TW_XY);
+					const tw_u32x2 cur = tw_ld64(u.pc);
+	#if defined(__HIP_DEVICE_COMPILE__)
+					__builtin_amdgcn_sched_barrier(0);                           // the differences wait for these two reads only, not for PF's
+	#endif
+					const tw_u32x2 pf = tw_ld64((t0 & 0x3f8u) + TW_PF);
+					const int spm1 = tw_ld_u8((u.pc >> 3) + L::SP_OF_XQ);        // ... and q_span - 1
+					const uint32_t drm1 = cur.x - xy.x, dqm1 = cur.y - xy.y;
+					const uint32_t ddl = tw_sad(drm1, dqm1, c_lut);
+					const uint32_t dqs = SAMEGAP ? dqm1 : __builtin_elementwise_add_sat(dqm1, c_dqoff);
+					const uint32_t m3 = max(max(drm1, dqs), ddl + c_cbwl);
+					const uint64_t okm = TW_ULT(m3, c_M);
+					const uint32_t dst = TW_SEL(okm, min(u.m4 - pf.x, c_far), c_far);
+					tw_st32(dst, (int)u.m4);
+					wave_mem_fence();
+					const int tj = tw_ld32(c_own);
+					const int lutv = tw_ld_i8(min(ddl, c_bwl) + LUT_OFF);
+	#if defined(__HIP_DEVICE_COMPILE__)
+					__builtin_amdgcn_sched_barrier(0);
+	#endif
+					const int sc0 = min(min((int)dqm1, (int)drm1), spm1);
+					const int sc = TW_SEL(okm, sc0 + (int)pf.y + lutv, c_min);
+					const int excl = max(tw_excl_max32(sc), spm1);
+					const uint64_t A = TW_SGT(sc, excl);
+					B = TW_EQ(tj, u.m4) & okm & ~A;
+					const uint64_t OUT = TW_SGE(drm1, c_Mout);
+					cB = tw_below_in_half(B, hi_half);
+					tile = 0; X = 0; a_cur = 0;
+					if (__builtin_expect((TW_SGT(cB, 0) & A) != 0, 0)) { force_general = true; break; }
+					a_cur = S1 & 0x3f8u;
+					{
+						const uint32_t wp = TW_SEL(A, u.m4 - c_own, 0xfffffffcu);
+						const int wf = TW_SEL(A, sc, spm1);
+						if (__builtin_amdgcn_inverse_ballot_w64(tw_last_or_lane0(A))) tw_st64(a_cur + TW_PF, wp, (uint32_t)wf);
+					}
+					X = (TW_SGE(cB, c_ms) & B) | OUT;
+					if (__builtin_expect(tw_both_halves(X) == 0, 0)) break;
+					u.m4 += 4u; u.S = S1;
+					u.pc += 8u; tile = TW_SGE(u.pc, u.pend);
+					TW_STAMP(if (g.stamp) ++st_n_fast;)
+					if (__builtin_expect(tile != 0, 0)) break;
+					wave_mem_fence();
+				}
+				if (!force_general && tile == 0) {
+					// a half wants its second chunk.  n_skip after the first: #B, as no A lane follows a B lane
+					svc = slow_tail(tw_smear_halves(X), a_cur + TW_PF, cB + (int)__builtin_amdgcn_inverse_ballot_w64(B));
+				}
 			}
 		} else {
 			// ------------------------------------------------------------ general pass: second chunks, idle halves, interleaved walks
 			force_general = false;
-			const uint32_t t0 = u.S - L16;
+			const uint32_t t0 = u.S + 16u - L16;                                  // (L16 is 16 (k + 1))
 			const uint32_t xcur = ((((u.m4 - c_mkbase) + 4u) << 2) & 0x7f8u) | c_8h;   // XY slot of anchor i (m4 = 4 (i - 1) + mark base)
 			const tw_u32x2 xy = tw_ld64((t0 & 0x7f8u) + TW_XY);
 			const tw_u32x2 pf = tw_ld64((t0 & 0x3f8u) + TW_PF);
