@@ -176,6 +176,20 @@ __device__ __forceinline__ uint64_t tw_above_first(uint64_t a, uint64_t b)
 	return a & ((uint64_t)hi << 32 | lo);
 }
 
+// The one exit test of the fast loop: k, or 0 where a half has an A lane above its lowest B lane (interleaved).  The s_and_b64 of
+// tw_above_first sets SCC, and the s_cselect reads it at once; `ia` keeps the interleave mask for the block behind the exit.
+__device__ __forceinline__ uint32_t tw_exit_key(uint64_t a, uint64_t b, uint32_t k, uint64_t &ia)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	uint32_t lo, hi;
+	asm("s_sub_i32 %0, 0, %2\n\ts_sub_i32 %1, 0, %3" : "=&s"(lo), "=&s"(hi) : "s"(TW_UNI((uint32_t)b)), "s"(TW_UNI((uint32_t)(b >> 32))) : "scc");
+	asm("s_and_b64 %1, %2, %3\n\ts_cselect_b32 %0, 0, %0" : "+s"(k), "=&s"(ia) : "s"(a), "s"((uint64_t)hi << 32 | lo) : "scc");
+#else
+	ia = tw_above_first(a, b); k = ia ? 0u : k;
+#endif
+	return k;
+}
+
 // ds_write_b64 of (x, y) to the PF ring (byte a + TW_PF) by the lanes of m alone, exec set by hand: as a branch on m it would be the one
 // divergent branch of the fast loop, and the compiler's structurizer would then merge the loop's uniform exits into flag registers
 __device__ __forceinline__ void tw_st64_pf_lanes(uint64_t m, uint32_t a, uint32_t x, uint32_t y)
@@ -289,16 +303,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 	uint32_t c_dqoff = c_M - mdq;
 	int c_ms = g.par.max_skip;
 	int c_min = INT_MIN;
-	int c_Mout = hl == 31 ? g.par.max_dist_x : INT_MAX;            // window test that only the half's last lane can fail
+	int c_Mout = hl == 31 ? g.par.max_dist_x : INT_MAX;            // (two tables) window test that only the half's last lane can fail
 	uint32_t c_bwl = c_bw + c_lut;                                 // table address of the last entry (- LUT_OFF)
 	uint32_t c_cbwl = c_cbw - c_lut;                               // (dd + c_lut) + this = dd + c_cbw
 	constexpr uint32_t LUT_OFF = ONE_LUT ? L::LUT : 0u;
-	// (one table: c_M and c_ms stay scalar -- only compares read them -- for the registers of the eighth wave)
+	// (one table: c_M and c_ms stay scalar -- only compares read them -- for the registers of the eighth wave, and there is no c_Mout:
+	// the fast pass' window test is off its common path, where a compare with c_M masked to lane 31 does)
 	TW_VREG(L16); TW_VREG(c_far); TW_VREG(c_own);
-	if (!ONE_LUT) { TW_VREG(c_M); TW_VREG(c_ms); }
+	if (!ONE_LUT) { TW_VREG(c_M); TW_VREG(c_ms); TW_VREG(c_Mout); }
 	if (!ONE_LUT) TW_VREG(c_lut);
 	if (!SAMEGAP) TW_VREG(c_dqoff);
-	TW_VREG(c_min); TW_VREG(c_Mout); TW_VREG(c_bwl); TW_VREG(c_cbwl);
+	TW_VREG(c_min); TW_VREG(c_bwl); TW_VREG(c_cbwl);
 
 	const uint64_t maxx = (uint64_t)(int64_t)g.par.max_dist_x;
 	// (uniform) which kernel takes the batch: k_chain_quad has written 1 before this kernel starts; the one-table layout takes
@@ -674,87 +689,124 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 				// Inside this loop u.S runs one anchor ahead (16 i + 8h: the S1 of the pass), so that it is updated in place; every exit
 				// puts it back.  Both halves advance one anchor per pass, so the tile test is a scalar count of the passes until either
 				// half's tile ends (at least one: the test behind every pass left both halves with anchors).
-				uint64_t B, D = 0;
-				bool tile_end = false;
+				//
+				// One exit, so that the compiler has no exits to merge into flag registers: a pass goes on iff it is not interleaved and
+				// min(#(B | E) lo, #(B | E) hi, passes left + ms0) > ms0, one scalar compare at the bottom of the inner loop.  Behind it, the
+				// rare block finds out why the inner loop stopped: interleaved (general pass), a half that does not break (lane-31 window
+				// test: if both halves' scans are complete the outer loop goes on), or the end of the stretch of passes (the tile's, or E's).
+				// u.S and u.m4 move on at the end of every pass and are taken back where the anchor is not done.
+				uint64_t B, D = 0, I, E = 0;
+				uint32_t drx;                                                    // dr - 1 of the pass the inner loop stopped at
+				bool tile_end = false;                                           // (or E's stretch: service() then finds no tile exhausted)
 				int npass = 1;
 				if constexpr (L::HAS_XQ) {
 					const int n0 = (int)(TW_UNI(__builtin_amdgcn_readlane((int)u.pend, 0)) - TW_UNI(__builtin_amdgcn_readlane((int)u.pc, 0))) >> 3;
 					const int n1 = (int)(TW_UNI(__builtin_amdgcn_readlane((int)u.pend, 32)) - TW_UNI(__builtin_amdgcn_readlane((int)u.pc, 32))) >> 3;
 					npass = max(min(n0, n1), 1);
 				} else {
-					const int n0 = (int)(TW_UNI(__builtin_amdgcn_readlane((int)u.pend, 0)) - TW_UNI(__builtin_amdgcn_readlane((int)u.m4, 0))) >> 2;
-					const int n1 = (int)(TW_UNI(__builtin_amdgcn_readlane((int)u.pend, 32)) - TW_UNI(__builtin_amdgcn_readlane((int)u.m4, 32))) >> 2;
+					const uint32_t m0 = TW_UNI(__builtin_amdgcn_readlane((int)u.m4, 0)), m1 = TW_UNI(__builtin_amdgcn_readlane((int)u.m4, 32));
+					const int n0 = (int)(TW_UNI(__builtin_amdgcn_readlane((int)u.pend, 0)) - m0) >> 2;
+					const int n1 = (int)(TW_UNI(__builtin_amdgcn_readlane((int)u.pend, 32)) - m1) >> 2;
 					npass = max(min(n0, n1), 1);
+					// a half whose anchor is one of its unit's first 32 (i <= 31) has its lane 31 on a slot from before the unit, which
+					// fails the window test: its scan is complete whether it breaks or not.  Such a half counts as having 32 B lanes (E)
+					// for the passes until its i reaches 32, and the stretch of passes ends there (the outer loop sets E again).
+					const int e0 = 31 - ((int)(m0 - L::MK) >> 2), e1 = 31 - ((int)(m1 - L::MK - TW_MK_HALF) >> 2);   // 32 - i (m4 = 4 (i - 1) + mark base)
+					if (e0 > 0) { E |= 0x00000000ffffffffull; npass = min(npass, e0); }
+					if (e1 > 0) { E |= 0xffffffff00000000ull; npass = min(npass, e1); }
 				}
 				const uint32_t ms0 = (uint32_t)max(g.par.max_skip, 0);           // a half's scan breaks in this chunk iff it has more B lanes
+				uint32_t P = (uint32_t)npass + ms0;                              // passes left + ms0 (npass <= 64: no wrap)
 				u.S += 16u;
 				for (;;) {
-					const uint32_t S1 = u.S;                                     // 16 i + 8h
-					const uint32_t t0 = S1 - L16;                                // lane k <-> predecessor j = i - 1 - k of its half's anchor
-					const tw_u32x2 xy = tw_ld64((t0 & 0x7f8u) + TW_XY);
-					// the anchor itself: one table, from its XY slot (x + 1, q + 1); two tables, from XQ (x, q)
-					const tw_u32x2 cur = tw_ld64(L::HAS_XQ ? u.pc : (S1 & 0x7f8u) + TW_XY);
+					uint32_t key;
+					do {
+						const uint32_t S1 = u.S;                                     // 16 i + 8h
+						const uint32_t t0 = S1 - L16;                                // lane k <-> predecessor j = i - 1 - k of its half's anchor
+						const tw_u32x2 xy = tw_ld64((t0 & 0x7f8u) + TW_XY);
+						// the anchor itself: one table, from its XY slot (x + 1, q + 1); two tables, from XQ (x, q)
+						const tw_u32x2 cur = tw_ld64(L::HAS_XQ ? u.pc : (S1 & 0x7f8u) + TW_XY);
 	#if defined(__HIP_DEVICE_COMPILE__)
-					__builtin_amdgcn_sched_barrier(0);                           // the differences wait for these two reads only, not for PF's
+						__builtin_amdgcn_sched_barrier(0);                           // the differences wait for these two reads only, not for PF's
 	#endif
-					const tw_u32x2 pf = tw_ld64((t0 & 0x3f8u) + TW_PF);
-					uint32_t a_cur = S1 & 0x3f8u;                                // PF slot of anchor i; one table: its SP byte is this / 8 (a shift:
-					TW_OPAQUE(a_cur);                                            // the compiler would make it a three-operand v_bfe from S1)
-					const int spm1 = tw_ld_u8(L::HAS_XQ ? (u.pc >> 3) + L::SP_OF_XQ : (a_cur >> 3) + L::SP);   // ... and q_span - 1
+						const tw_u32x2 pf = tw_ld64((t0 & 0x3f8u) + TW_PF);
+						uint32_t a_cur = S1 & 0x3f8u;                                // PF slot of anchor i; one table: its SP byte is this / 8 (a shift:
+						TW_OPAQUE(a_cur);                                            // the compiler would make it a three-operand v_bfe from S1)
+						const int spm1 = tw_ld_u8(L::HAS_XQ ? (u.pc >> 3) + L::SP_OF_XQ : (a_cur >> 3) + L::SP);   // ... and q_span - 1
 	#ifdef TW_EXP_PAD
-					// experiment: TW_EXP_PAD dependence-free half-rate VALU instructions (three sources; the result is dropped)
-					for (int k = 0; k < TW_EXP_PAD; ++k) { uint32_t pad; asm volatile("v_max3_u32 %0, %1, %1, %1" : "=v"(pad) : "v"(c_far)); }
+						// experiment: TW_EXP_PAD dependence-free half-rate VALU instructions (three sources; the result is dropped)
+						for (int k = 0; k < TW_EXP_PAD; ++k) { uint32_t pad; asm volatile("v_max3_u32 %0, %1, %1, %1" : "=v"(pad) : "v"(c_far)); }
 	#endif
-					// differences minus one (the ring holds x + 1, q + 1)
-					const uint32_t drm1 = L::HAS_XQ ? cur.x - xy.x : tw_sub_m1(cur.x, xy.x), dqm1 = L::HAS_XQ ? cur.y - xy.y : tw_sub_m1(cur.y, xy.y);
-					const uint32_t ddl = ONE_LUT ? tw_absdiff(drm1, dqm1) : tw_sad(drm1, dqm1, c_lut);   // |dr - dq| + the half's table base
-					const uint32_t dqs = SAMEGAP ? dqm1 : __builtin_elementwise_add_sat(dqm1, c_dqoff);
-					const uint32_t m3 = max(max(drm1, dqs), ddl + c_cbwl);
-					const uint64_t okm = TW_ULT(m3, c_M);                        // chain.c:252-260 as one compare
-					// the mark round trip (chain.c:281: store by distance, the others to the sink; then the lane's own word) and the table
-					// lookup are issued back to back, before anything waits for either
-					const uint32_t dst = TW_SEL(okm, min(u.m4 - pf.x, c_far), c_far);
-					tw_st32(dst, (int)u.m4);
-					wave_mem_fence();
-					const int tj = tw_ld32(c_own);
-					const int lutv = tw_ld_i8(min(ddl, c_bwl) + LUT_OFF);
+						// differences minus one (the ring holds x + 1, q + 1)
+						const uint32_t drm1 = L::HAS_XQ ? cur.x - xy.x : tw_sub_m1(cur.x, xy.x), dqm1 = L::HAS_XQ ? cur.y - xy.y : tw_sub_m1(cur.y, xy.y);
+						drx = drm1;
+						const uint32_t ddl = ONE_LUT ? tw_absdiff(drm1, dqm1) : tw_sad(drm1, dqm1, c_lut);   // |dr - dq| + the half's table base
+						const uint32_t dqs = SAMEGAP ? dqm1 : __builtin_elementwise_add_sat(dqm1, c_dqoff);
+						const uint32_t m3 = max(max(drm1, dqs), ddl + c_cbwl);
+						const uint64_t okm = TW_ULT(m3, c_M);                        // chain.c:252-260 as one compare
+						// the mark round trip (chain.c:281: store by distance, the others to the sink; then the lane's own word) and the table
+						// lookup are issued back to back, before anything waits for either
+						const uint32_t dst = TW_SEL(okm, min(u.m4 - pf.x, c_far), c_far);
+						tw_st32(dst, (int)u.m4);
+						wave_mem_fence();
+						const int tj = tw_ld32(c_own);
+						const int lutv = tw_ld_i8(min(ddl, c_bwl) + LUT_OFF);
 	#if defined(__HIP_DEVICE_COMPILE__)
-					__builtin_amdgcn_sched_barrier(0);
+						__builtin_amdgcn_sched_barrier(0);
 	#endif
-					const int sc0 = min(min((int)dqm1, (int)drm1), spm1);        // chain.c:262-263, minus one
-					const int sc = TW_SEL(okm, sc0 + (int)pf.y + lutv, c_min);   // chain.c:272-273 via the table, minus one (the ring holds f - 1)
-					const int excl = max(tw_excl_max32(sc), spm1);               // (q_span - 1 >= 0: the scan's zero fill stays below it)
-					const uint64_t A = TW_SGT(sc, excl);                         // new running max (chain.c:274); masked lanes hold INT_MIN
-					B = TW_EQ(tj, u.m4) & okm & ~A;                              // marked and not better (chain.c:277)
-					// n_skip walk (chain.c:276,278) from n_skip = 0.  When every A lane of a half precedes every B lane of it, n_skip at a
-					// B lane is the number of B lanes up to it: the break is the (max_skip + 1)-th of them.  An A lane above a B lane
-					// (interleaved, rare) leaves this loop for the general pass, which redoes the anchor.  Both tests are on the scalar side:
-					// interleaved iff a half has an A lane above its lowest B lane, and a half breaks iff it has more than max_skip B lanes.
-					const uint32_t blo = (uint32_t)B, bhi = (uint32_t)(B >> 32);
-					if (__builtin_expect(tw_above_first(A, B) != 0, 0)) { force_general = true; break; }
-					// the running max goes to PF[i]: the half's last A lane writes its own score and predecessor, or (none) the half's
-					// lane 0 writes "no predecessor, q_span" (minus one).  f is max(excl, sc) either way: sc > excl at an A lane, and at lane 0
-					// of a half without one, sc <= excl = q_span - 1
-					{
-						const uint32_t wp = TW_SEL(A, u.m4 - c_own, 0xfffffffcu);      // 4 j of the lane's predecessor: 4 (i - 1 - k)
-						const int wf = max(excl, sc);
-						tw_st64_pf_lanes(tw_last_or_lane0(A), a_cur, wp, (uint32_t)wf);
-					}
+						const int sc0 = min(min((int)dqm1, (int)drm1), spm1);        // chain.c:262-263, minus one
+						const int sc = TW_SEL(okm, sc0 + (int)pf.y + lutv, c_min);   // chain.c:272-273 via the table, minus one (the ring holds f - 1)
+						const int excl = max(tw_excl_max32(sc), spm1);               // (q_span - 1 >= 0: the scan's zero fill stays below it)
+						const uint64_t A = TW_SGT(sc, excl);                         // new running max (chain.c:274); masked lanes hold INT_MIN
+						B = TW_EQ(tj, u.m4) & okm & ~A;                              // marked and not better (chain.c:277)
+						// n_skip walk (chain.c:276,278) from n_skip = 0.  When every A lane of a half precedes every B lane of it, n_skip at a
+						// B lane is the number of B lanes up to it: the break is the (max_skip + 1)-th of them.  An A lane above a B lane
+						// (interleaved, rare) sends the anchor to the general pass, which redoes it.  Both tests are on the scalar side, in the
+						// exit test below: interleaved iff a half has an A lane above its lowest B lane, and a half breaks iff it has more than
+						// max_skip B lanes.
+						//
+						// The running max goes to PF[i]: the half's last A lane writes its own score and predecessor, or (none) the half's
+						// lane 0 writes "no predecessor, q_span" (minus one).  f is max(excl, sc) either way: sc > excl at an A lane, and at lane 0
+						// of a half without one, sc <= excl = q_span - 1.  An interleaved pass writes it too: the general pass that redoes the
+						// anchor writes PF[i] of both halves before anything reads it.
+						{
+							const uint32_t wp = TW_SEL(A, u.m4 - c_own, 0xfffffffcu);      // 4 j of the lane's predecessor: 4 (i - 1 - k)
+							const int wf = max(excl, sc);
+							tw_st64_pf_lanes(tw_last_or_lane0(A), a_cur, wp, (uint32_t)wf);
+						}
+#ifdef TW_EXP_SPAD
+						// experiment: TW_EXP_SPAD dependence-free scalar ALU instructions (a scratch SGPR; no memory, no VALU)
+						for (int k = 0; k < TW_EXP_SPAD; ++k) { uint32_t pad; asm volatile("s_xor_b32 %0, %0, %0" : "=s"(pad) :: "scc"); }
+#endif
+						u.m4 += 4u; u.S += 16u;
+						--P;
+						const uint64_t BE = B | E;
+						uint32_t nmin = min((uint32_t)__builtin_popcount((uint32_t)BE), (uint32_t)__builtin_popcount((uint32_t)(BE >> 32)));
+	#if defined(__HIP_DEVICE_COMPILE__)
+						asm("" : "+s"(nmin));                                        // (else the two mins become a v_min3 and a v_readfirstlane)
+	#endif
+						key = tw_exit_key(A, B, min(nmin, P), I);
+						TW_STAMP(if (g.stamp && key > ms0) ++st_n_fast;)
+						wave_mem_fence();
+					} while (__builtin_expect(key > ms0, 1));
+					// why the pass stopped.  Interleaved: the general pass redoes the anchor
+					if (I != 0) { force_general = true; break; }
 					// scan complete: break taken, or the half's last lane is outside the window (x is sorted: nothing older can matter).
-					// The window test only matters for a half that does not break, so it waits behind the count.
-					const uint32_t nlo = (uint32_t)__builtin_popcount(blo), nhi = (uint32_t)__builtin_popcount(bhi);
-					if (__builtin_expect(min(nlo, nhi) <= ms0, 0)) {
-						const uint64_t OUT = TW_SGE(drm1, c_Mout);               // the half's last lane is outside the window (or no anchor there yet)
+					// The window test only matters for a half that does not break.
+					const uint32_t nlo = (uint32_t)__builtin_popcount((uint32_t)B), nhi = (uint32_t)__builtin_popcount((uint32_t)(B >> 32));
+					if (min(nlo, nhi) <= ms0) {
+						const uint64_t OUT = TW_SGE(drx, c_M) & TW_HI31;         // the half's last lane is outside the window (or no anchor there yet)
 						D = tw_smear_halves(OUT | (nlo > ms0 ? 0x00000000ffffffffull : 0ull) | (nhi > ms0 ? 0xffffffff00000000ull : 0ull));
-						if (__builtin_expect(tw_both_halves(D) == 0, 0)) break;
+						if (tw_both_halves(D) == 0) break;
 					}
-					u.m4 += 4u; u.S += 16u;
-					if constexpr (L::HAS_XQ) u.pc += 8u;
+					// both halves' scans are complete: the next anchor, unless the tile ends
 					TW_STAMP(if (g.stamp) ++st_n_fast;)
-					if (__builtin_expect(--npass <= 0, 0)) { tile_end = true; break; }
+					if (P <= ms0) { tile_end = true; break; }
 					wave_mem_fence();
 				}
-				const uint32_t a_cur = u.S & 0x3f8u;                             // PF slot of the anchor the loop stopped at (no tile end)
+				TW_OPAQUE(u.S); TW_OPAQUE(u.m4);                                 // (else the compiler keeps the pass' S1 and m4 live out of the loop)
+				if (!tile_end) { u.m4 -= 4u; u.S -= 16u; }                        // the anchor the loop stopped at is not done
+				const uint32_t a_cur = u.S & 0x3f8u;                             // its PF slot (no tile end)
 				u.S -= 16u;
 				if (!force_general && !tile_end) {
 					// a half wants its second chunk.  n_skip after the first: #B, as no A lane follows a B lane
