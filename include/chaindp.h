@@ -247,6 +247,37 @@ int chaindp_map_reads(chaindp_ctx_t *ctx, const chaindp_index_t *idx, int flag, 
                       const int32_t *qlen, const uint32_t *hash, const int32_t *ref_len, int32_t n_ref, int64_t *regs_off, chaindp_reg_t *regs,
                       int64_t regs_cap, int32_t *rep_len, int64_t *n_anchors);
 
+/* ---- sketch on the GPU: bases in, minimizers resident (mm_sketch, sketch.c:77-143, as collect_minimizers calls it, map.c:87-99) -------
+ * What the host had to do per base before chaindp_collect_seeds: here for a whole batch, parallel inside every sequence, the result
+ * identical to the reference's in content and order (x = hash64(kmer) << 8 | span, y = rid << 32 | lastPos << 1 | strand, plus the
+ * shift of the segments after a read's first).
+ *   seq: the bases as mm_bseq1_t::seq holds them, one byte each, any value (A C G T U in either case and the bytes 0..3 are bases,
+ *   everything else is ambiguous), all sequences concatenated; seq_off[n_seqs + 1] their offsets.  w 1..255, k 1..28, is_hpc as
+ *   mm_sketch takes them.  n_segs_per_read may be NULL (every read is one sequence); otherwise read r owns n_segs_per_read[r]
+ *   consecutive sequences, rid = the segment's index in its read (map.c:92).  A sequence without a valid k-mer (also an empty
+ *   one) has no minimizers.  mini_off[n_reads + 1] receives the CSR offsets; the minimizers stay in HBM.
+ * chaindp_collect_seeds, chaindp_map_batch and chaindp_map_reads take them from there when called with mini == NULL and
+ * mini_off == NULL (n_reads must match; qlen == NULL then means the read lengths chaindp_sketch saw).  They stay valid until the
+ * next chaindp_sketch or the next call that uploads minimizers of its own.
+ * A sketch starts a new batch: whatever batch was resident in ctx is dropped before anything is overwritten -- chaindp_download,
+ * chaindp_backtrack, chaindp_gen_regs ... are refused (CHAINDP_ERR_ARG) and chaindp_download_anchors / _mini_pos return nothing
+ * until a new batch has been collected and run.  Download what you need of a batch before sketching the next one in the same context.
+ * The buffers grow with the batch (about 45 bytes per base); CHAINDP_ERR_CAPACITY if the batch has more reads than ctx was created
+ * for, 2^31 bases or more, or more than the device has room for -- the context stays usable.
+ * Not done here: mm_dust_minier (opt->sdust_thres is 0 in every preset), the index-side sketch, 2-bit packed input.  Synchronous. */
+int chaindp_sketch(chaindp_ctx_t *ctx, int w, int k, int is_hpc, int64_t n_seqs, const int64_t *seq_off, const char *seq,
+                   const int32_t *n_segs_per_read, int64_t *mini_off /* [n_reads + 1] */);
+int chaindp_download_minimizers(chaindp_ctx_t *ctx, chaindp_anchor_t *mini);   /* mini_off[n_reads] entries */
+/* chaindp_sketch followed by chaindp_map_reads in one call, single-segment reads: bases in, the reference's final hits of a
+ * non-CIGAR run out.  w, k, is_hpc = mi->w, mi->k, mi->flag & MM_I_HPC; the other arguments as chaindp_map_reads'.  Bit-identical
+ * to the separate calls. */
+int chaindp_map_seqs(chaindp_ctx_t *ctx, const chaindp_index_t *idx, int w, int k, int is_hpc, int flag, int max_occ, const chaindp_params_t *par,
+                     int min_cnt, const chaindp_post_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seq, const uint32_t *bid,
+                     const uint32_t *hash, const int32_t *ref_len, int32_t n_ref, int64_t *regs_off, chaindp_reg_t *regs, int64_t regs_cap,
+                     int32_t *rep_len, int64_t *n_anchors);
+/* With profiling on (chaindp_set_profiling): device time of the sketch kernels and scans accumulated over `calls` chaindp_sketch calls. */
+int chaindp_get_sketch_ms(chaindp_ctx_t *ctx, double *ms, int64_t *calls, int reset);
+
 /* Exists for tests: the device's logf of the integers 1..kmax (kmax <= 2^24) -- (float)log((double)k) patched where the host's logf
  * rounds differently -- and mm_set_mapq's n_sub term of them ((int)(4.343f * logf(k) + .499f), hit.c:474) compared with the host's;
  * returns the number of integers where either differs (>= 0) or an error code. */

@@ -30,6 +30,7 @@ ABI_SYMBOLS = (
     "chaindp_pipe_create", "chaindp_pipe_destroy", "chaindp_pipe_submit", "chaindp_pipe_wait", "chaindp_pipe_release",
     "chaindp_pipe_last_error", "chaindp_map_batch",
     "chaindp_chain_post", "chaindp_map_reads", "chaindp_post_logf_selftest", "chaindp_post_logf_patches",
+    "chaindp_sketch", "chaindp_download_minimizers", "chaindp_map_seqs", "chaindp_get_sketch_ms",
 )
 
 # chaindp_reg_t == mm_reg1_t (minimap.h:100-115), 80 bytes; `bits` is the bit-field word (rev = bit 10)
@@ -97,6 +98,10 @@ def lib():
         PO = C.POINTER(PostOpt)
         L.chaindp_chain_post.argtypes = [vp, PO, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp]
         L.chaindp_map_reads.argtypes = [vp, vp, i32, i32, P, i32, PO, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, i64, vp, vp]
+        L.chaindp_sketch.argtypes = [vp, i32, i32, i32, i64, vp, vp, vp, vp]
+        L.chaindp_download_minimizers.argtypes = [vp, vp]
+        L.chaindp_map_seqs.argtypes = [vp, vp, i32, i32, i32, i32, i32, P, i32, PO, i64, vp, vp, vp, vp, vp, i32, vp, vp, i64, vp, vp]
+        L.chaindp_get_sketch_ms.argtypes = [vp, vp, vp, i32]
         L.chaindp_post_logf_selftest.restype = i64
         L.chaindp_post_logf_selftest.argtypes = [vp, i32]
         L.chaindp_post_logf_patches.restype = i64
@@ -144,7 +149,7 @@ class Device:
             raise ChainDPError(self._lib.chaindp_last_error(None).decode())
         self.device = device
         self.max_anchors, self.max_reads = max_anchors, max_reads
-        self._n_reads = self._total = 0
+        self._n_reads = self._total = self._sk_n_mini = 0
         self._indexes = []
         if ring is not None:
             self._check(self._lib.chaindp_set_ring(self._ctx, ring))
@@ -271,11 +276,15 @@ class Device:
 
     def collect_seeds(self, index, flag, max_occ, mini_off, mini, bid, qlen, n_segs=None):
         """Minimizers of a batch -> sorted anchors resident on the device (as after upload()).  Returns (off int64[n_reads+1],
-        anchors uint64[n,2], rep_len int32[n_reads], mini_pos_off, mini_pos uint64[...])."""
-        mini_off = np.ascontiguousarray(mini_off, np.int64)
-        n_reads = len(mini_off) - 1
-        mini = np.ascontiguousarray(mini, np.uint64).reshape(-1, 2)
-        bid = np.ascontiguousarray(bid, np.uint32); qlen = np.ascontiguousarray(qlen, np.int32)
+        anchors uint64[n,2], rep_len int32[n_reads], mini_pos_off, mini_pos uint64[...]).  mini_off = mini = None: the minimizers the last
+        sketch() left on the device (qlen = None then: the lengths it saw)."""
+        if mini_off is None and mini is None:
+            n_reads = len(bid)
+        else:
+            mini_off = np.ascontiguousarray(mini_off, np.int64)
+            n_reads = len(mini_off) - 1
+            mini = np.ascontiguousarray(mini, np.uint64).reshape(-1, 2)
+        bid = np.ascontiguousarray(bid, np.uint32); qlen = None if qlen is None else np.ascontiguousarray(qlen, np.int32)
         off = np.zeros(n_reads + 1, np.int64); mpo = np.zeros(n_reads + 1, np.int64); rep = np.zeros(max(n_reads, 1), np.int32)
         ns = None if n_segs is None else np.ascontiguousarray(n_segs, np.int32)
         self._check(self._lib.chaindp_collect_seeds(self._ctx, index, int(flag), int(max_occ), n_reads, _ptr(mini_off), _ptr(mini), _ptr(bid),
@@ -331,13 +340,19 @@ class Device:
 
     def map_reads(self, index, flag, max_occ, par, min_cnt, opt, mini_off, mini, bid, qlen, hash_, ref_len, regs_cap=None):
         """Minimizers in, final hits out (chaindp_map_reads): (regs_off int64[n_reads+1], regs REG_DTYPE[...], rep_len int32[n_reads],
-        n_anchors).  regs_cap None: a guess from the minimizer count, retried with the exact count if the hits need more."""
-        mini_off = np.ascontiguousarray(mini_off, np.int64)
-        n_reads = len(mini_off) - 1
-        mini = np.ascontiguousarray(mini, np.uint64).reshape(-1, 2)
-        bid = np.ascontiguousarray(bid, np.uint32); qlen = np.ascontiguousarray(qlen, np.int32); hash_ = np.ascontiguousarray(hash_, np.uint32)
+        n_anchors).  regs_cap None: a guess from the minimizer count, retried with the exact count if the hits need more.
+        mini_off = mini = None: the minimizers the last sketch() left on the device (qlen = None then: the lengths it saw)."""
+        if mini_off is None and mini is None:
+            n_reads, n_mini = len(bid), self._sk_n_mini
+        else:
+            mini_off = np.ascontiguousarray(mini_off, np.int64)
+            n_reads = len(mini_off) - 1
+            mini = np.ascontiguousarray(mini, np.uint64).reshape(-1, 2)
+            n_mini = len(mini)
+        bid = np.ascontiguousarray(bid, np.uint32); hash_ = np.ascontiguousarray(hash_, np.uint32)
+        qlen = None if qlen is None else np.ascontiguousarray(qlen, np.int32)
         ref_len = np.ascontiguousarray(ref_len, np.int32)
-        cap = int(regs_cap) if regs_cap is not None else max(len(mini) // 4, 1024)
+        cap = int(regs_cap) if regs_cap is not None else max(n_mini // 4, 1024)
         roff = np.zeros(n_reads + 1, np.int64); rep = np.zeros(max(n_reads, 1), np.int32)
         regs = np.zeros(max(cap, 1), REG_DTYPE)
         na = C.c_int64(0)
@@ -350,6 +365,56 @@ class Device:
         else:
             self._check(rc)
         return roff, regs[:int(roff[-1])], rep[:n_reads], int(na.value)
+
+    # -- sketch on the device: bases in, minimizers resident (chaindp_sketch)
+    @staticmethod
+    def _seqs(seq, seq_off):
+        if isinstance(seq, (bytes, bytearray)):
+            seq = np.frombuffer(seq, np.uint8)
+        return np.ascontiguousarray(seq, np.uint8), np.ascontiguousarray(seq_off, np.int64)
+
+    def sketch(self, w, k, is_hpc, seq, seq_off, n_segs=None):
+        """mm_sketch of a batch of sequences (bytes or uint8, concatenated; seq_off int64[n_seqs+1]) -> mini_off int64[n_reads+1]; the
+        minimizers stay on the device for collect_seeds / map_reads with mini_off = mini = None, download_minimizers() fetches them."""
+        seq, seq_off = self._seqs(seq, seq_off)
+        ns = None if n_segs is None else np.ascontiguousarray(n_segs, np.int32)
+        n_reads = len(seq_off) - 1 if ns is None else len(ns)
+        mini_off = np.zeros(n_reads + 1, np.int64)
+        self._check(self._lib.chaindp_sketch(self._ctx, int(w), int(k), int(bool(is_hpc)), len(seq_off) - 1, _ptr(seq_off), _ptr(seq) if len(seq) else None,
+                                             _ptr(ns), _ptr(mini_off)))
+        self._sk_n_mini = int(mini_off[-1])
+        return mini_off
+
+    def download_minimizers(self):
+        """uint64[n, 2] (x, y) of the last sketch()."""
+        m = np.zeros((max(self._sk_n_mini, 1), 2), np.uint64)
+        self._check(self._lib.chaindp_download_minimizers(self._ctx, _ptr(m)))
+        return m[:self._sk_n_mini]
+
+    def map_seqs(self, index, w, k, is_hpc, flag, max_occ, par, min_cnt, opt, seq, seq_off, bid, hash_, ref_len, regs_cap=None):
+        """Bases in, final hits out (chaindp_map_seqs = sketch() + map_reads()): (regs_off, regs, rep_len, n_anchors)."""
+        seq, seq_off = self._seqs(seq, seq_off)
+        n_reads = len(seq_off) - 1
+        bid = np.ascontiguousarray(bid, np.uint32); hash_ = np.ascontiguousarray(hash_, np.uint32); ref_len = np.ascontiguousarray(ref_len, np.int32)
+        cap = int(regs_cap) if regs_cap is not None else max(len(seq) // 32, 1024)
+        roff = np.zeros(n_reads + 1, np.int64); rep = np.zeros(max(n_reads, 1), np.int32)
+        regs = np.zeros(max(cap, 1), REG_DTYPE)
+        na = C.c_int64(0)
+        rc = self._lib.chaindp_map_seqs(self._ctx, index, int(w), int(k), int(bool(is_hpc)), int(flag), int(max_occ), C.byref(par), int(min_cnt), C.byref(opt),
+                                        n_reads, _ptr(seq_off), _ptr(seq) if len(seq) else None, _ptr(bid), _ptr(hash_), _ptr(ref_len) if len(ref_len) else None,
+                                        len(ref_len), _ptr(roff), _ptr(regs), cap, _ptr(rep), C.byref(na))
+        self._n_reads, self._total = n_reads, int(na.value)
+        if rc == -2 and int(roff[-1]) > cap:                                   # more hits than guessed: run the post steps again with room for them
+            roff, regs = self.chain_post(opt, ref_len, regs_cap=int(roff[-1]))
+        else:
+            self._check(rc)
+        return roff, regs[:int(roff[-1])], rep[:n_reads], int(na.value)
+
+    def sketch_ms(self, reset=False):
+        """(device ms, calls) of the sketch kernels accumulated while profiling is on."""
+        ms, n = C.c_double(0), C.c_int64(0)
+        self._check(self._lib.chaindp_get_sketch_ms(self._ctx, C.byref(ms), C.byref(n), int(reset)))
+        return ms.value, int(n.value)
 
     def post_logf_selftest(self, kmax=1 << 24):
         """Mismatches of the device's logf of the integers 1..kmax against the host's (0 expected)."""

@@ -98,6 +98,19 @@ struct chaindp_ctx {
 	uint32_t *d_logf_k = nullptr;
 	float *d_logf_v = nullptr;
 	int n_logf = -1;
+	// sketch (allocated on first use, grown with the batch)
+	chaindp::SketchArgs sk = {};
+	std::vector<void*> sk_allocs;
+	int64_t sk_cap_bases = -1, sk_cap_chunks = -1, sk_cap_seqs = -1;
+	int64_t sk_max_bases = 0x7fffff00;         // CHAINDP_SKETCH_MAX_BASES (test switch) lowers it; positions and ranks are 32-bit
+	unsigned long long *d_sk_totals = nullptr;
+	bool sk_valid = false;                     // d_mini / d_mini_off hold what the last chaindp_sketch made
+	int64_t sk_n_reads = 0, sk_n_mini = 0;
+	std::vector<int64_t> sk_mini_off;          // its mini_off and the reads' lengths, for the calls that say "the resident ones"
+	std::vector<int32_t> sk_qlen;
+	hipEvent_t sk_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around the two phases of a sketch while profiling is on (created once)
+	double sk_ms = 0;
+	int64_t sk_calls = 0;
 	// profiling
 	bool prof = false;
 	std::vector<EventSet> pending;
@@ -161,6 +174,9 @@ extern "C" void chaindp_destroy(chaindp_ctx_t *ctx)
 	void *sbufs[] = {ctx->seed.kept, ctx->seed.used, ctx->seed.src, ctx->seed.mstate, ctx->seed.tile_tmp, ctx->seed.totals, ctx->seed.stacks,
 	                 ctx->d_mini, ctx->d_mini_off, ctx->d_mp_off, ctx->d_bid, ctx->d_qlen, ctx->d_rep_len, ctx->d_mini_pos};
 	for (void *b : sbufs) if (b) (void)hipFree(b);
+	for (void *b : ctx->sk_allocs) if (b) (void)hipFree(b);
+	if (ctx->d_sk_totals) (void)hipFree(ctx->d_sk_totals);
+	for (hipEvent_t e : ctx->sk_ev) if (e) (void)hipEventDestroy(e);
 	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
 	delete ctx;
 }
@@ -216,6 +232,7 @@ extern "C" chaindp_ctx_t *chaindp_create(int device, int64_t max_anchors, int64_
 	ctx->use_quad = getenv("CHAINDP_QUAD") != nullptr;
 	ctx->deep_handover = getenv("CHAINDP_NO_DEEP_HANDOVER") == nullptr;      // diagnostic switches are read here, once per context:
 	if (const char *v = getenv("CHAINDP_TWIN_FORCE_LEFT")) ctx->twin_force_left = atoi(v) == 2 ? 2 : 1;   // never on the launch path (contexts run from several host threads)
+	if (const char *v = getenv("CHAINDP_SKETCH_MAX_BASES")) { const long long m = atoll(v); if (m >= 0 && m < ctx->sk_max_bases) ctx->sk_max_bases = m; }
 	if (e != hipSuccess) {
 		g_create_error = std::string("chaindp_create: ") + hipGetErrorString(e);
 		chaindp_destroy(ctx);
@@ -972,7 +989,9 @@ extern "C" void chaindp_index_destroy(chaindp_index_t *ix)
 	delete ix;
 }
 
-static int seed_reserve(chaindp_ctx *ctx, int64_t n_mini)
+// oom_is_capacity: a failed allocation of the per-minimizer buffers is reported as CHAINDP_ERR_CAPACITY (chaindp_sketch's contract)
+// with every one of them released, so that the next call starts from nothing
+static int seed_reserve(chaindp_ctx *ctx, int64_t n_mini, bool oom_is_capacity = false)
 {
 	if (!ctx->seed_ready) {
 		// first use: all or nothing, as in compact_launch
@@ -1000,13 +1019,16 @@ static int seed_reserve(chaindp_ctx *ctx, int64_t n_mini)
 		for (void **g : grow) if (*g) { HIP_TRY(ctx, hipFree(*g)); *g = nullptr; }
 		ctx->seed_cap_mini = 0;
 		const size_t n = (size_t)n_mini + (size_t)n_mini / 4 + 1024;
-		HIP_TRY(ctx, hipMalloc((void**)&ctx->seed.kept, n * 8));
-		HIP_TRY(ctx, hipMalloc((void**)&ctx->seed.used, n * 8));
-		HIP_TRY(ctx, hipMalloc((void**)&ctx->seed.src, n * 8));
-		HIP_TRY(ctx, hipMalloc((void**)&ctx->seed.mstate, n * 8));
-		HIP_TRY(ctx, hipMalloc((void**)&ctx->seed.tile_tmp, (n / 1024 + 2) * 8));
-		HIP_TRY(ctx, hipMalloc((void**)&ctx->d_mini, n * 16));
-		HIP_TRY(ctx, hipMalloc((void**)&ctx->d_mini_pos, n * 8));
+		const size_t each[7] = {n * 8, n * 8, n * 8, n * 8, (n / 1024 + 2) * 8, n * 16, n * 8};
+		for (int k = 0; k < 7; ++k) {
+			const hipError_t e = hipMalloc(grow[k], each[k]);
+			if (e == hipSuccess) continue;
+			if (!oom_is_capacity) { ctx->err = std::string("hipMalloc (seed collection buffers): ") + hipGetErrorString(e); return CHAINDP_ERR_HIP; }
+			(void)hipGetLastError();
+			for (void **g : grow) if (*g) { (void)hipFree(*g); *g = nullptr; }
+			ctx->err = std::string("minimizer buffers for ") + std::to_string((long long)n_mini) + " minimizers: " + hipGetErrorString(e);
+			return CHAINDP_ERR_CAPACITY;
+		}
 		ctx->seed_cap_mini = (int64_t)n;
 	}
 	return CHAINDP_OK;
@@ -1020,16 +1042,27 @@ static int collect_seeds_impl(chaindp_ctx *ctx, const chaindp_index_t *ix, int f
 {
 	if (!ctx) return CHAINDP_ERR_ARG;
 	if (!ix || ix->device != ctx->device) { ctx->err = "index image missing or on another device"; return CHAINDP_ERR_ARG; }
+	// mini == NULL && mini_off == NULL: the minimizers the last chaindp_sketch left in this context (qlen == NULL: the lengths it saw)
+	const bool resident = !mini && !mini_off && !read_mini;
+	if (resident) {
+		if (!ctx->sk_valid || n_reads != ctx->sk_n_reads) { ctx->err = "no minimizers of a chaindp_sketch of n_reads reads are resident in this context"; return CHAINDP_ERR_ARG; }
+		mini_off = ctx->sk_mini_off.data();
+		if (!qlen) qlen = ctx->sk_qlen.data();
+	}
 	if (n_reads < 0 || !mini_off || (n_reads > 0 && (mini_off[0] != 0 || !bid || !qlen))) { ctx->err = "bad minimizer offsets"; return CHAINDP_ERR_ARG; }
 	const int64_t n_mini = n_reads > 0 ? mini_off[n_reads] : 0;
-	if (n_mini < 0 || (n_mini > 0 && !mini && !read_mini)) { ctx->err = "bad minimizers"; return CHAINDP_ERR_ARG; }
+	if (n_mini < 0 || (n_mini > 0 && !mini && !read_mini && !resident)) { ctx->err = "bad minimizers"; return CHAINDP_ERR_ARG; }
 	if (n_reads > ctx->cap_reads) { ctx->err = "batch exceeds the capacity the context was created with"; return CHAINDP_ERR_CAPACITY; }
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	int rc = seed_reserve(ctx, n_mini);
 	if (rc) return rc;
 	hipStream_t st = ctx->stream;
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mini_off, mini_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-	if (n_mini && read_mini) {                                     // one kernel pulls every read's minimizers out of its pinned buffer
+	if (!resident) {
+		ctx->sk_valid = false;                                     // d_mini is about to hold the caller's minimizers
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mini_off, mini_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
+	}
+	if (resident) {                                                // they are where the sketch wrote them: d_mini, d_mini_off
+	} else if (n_mini && read_mini) {                                     // one kernel pulls every read's minimizers out of its pinned buffer
 		rc = stage_pointers(ctx, (const void *const *)read_mini, n_reads);
 		if (rc) return rc;
 		HIP_TRY(ctx, chaindp::launch_gather_reads(st, n_reads, ctx->d_mini_off, (const void *const *)ctx->d_ptrs, ctx->d_mini));
@@ -1105,6 +1138,7 @@ extern "C" int chaindp_map_batch(chaindp_ctx_t *ctx, const chaindp_index_t *ix, 
 	int rc = check_params(ctx, par);
 	if (rc) return rc;
 	if (!regs_off || regs_cap < 0 || (regs_cap > 0 && !regs) || (n_reads > 0 && !hash)) { ctx->err = "NULL output or hash"; return CHAINDP_ERR_ARG; }
+	if (!mini && !mini_off && !qlen && ctx->sk_valid && n_reads == ctx->sk_n_reads) qlen = ctx->sk_qlen.data();   // the resident sketch's (checked below)
 	// seeds (resident), DP + compaction, chains, hits: every stage reads what the one before left in HBM
 	if ((rc = collect_seeds_impl(ctx, ix, flag, max_occ, n_reads, mini_off, mini, nullptr, bid, qlen, nullptr, nullptr, rep_len, nullptr)) != CHAINDP_OK) return rc;
 	if (n_anchors) *n_anchors = ctx->total;
@@ -1143,6 +1177,179 @@ extern "C" int chaindp_download_anchors(chaindp_ctx_t *ctx, chaindp_anchor_t *a)
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	if (ctx->total) HIP_TRY(ctx, hipMemcpyAsync(a, ctx->d_a, (size_t)ctx->total * 16, hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return CHAINDP_OK;
+}
+
+// ---- sketch on the GPU (include/chaindp.h): bases in, minimizers resident
+
+template <typename T>
+static hipError_t sk_alloc(chaindp_ctx *ctx, T *&p, size_t bytes)
+{
+	void *q = nullptr;
+	hipError_t e = hipMalloc(&q, bytes ? bytes : 8);
+	if (e == hipSuccess) { ctx->sk_allocs.push_back(q); p = (T*)q; }
+	return e;
+}
+
+// Buffers for a batch of n_bases bases in n_chunks chunks of n_seqs sequences.  All or nothing: when an allocation fails everything
+// is released, so that the context is as it was before its first sketch.
+static int sketch_reserve(chaindp_ctx *ctx, int64_t n_bases, int64_t n_chunks, int64_t n_seqs)
+{
+	if (!ctx->d_sk_totals) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_sk_totals, 4 * 8));
+	if (n_bases <= ctx->sk_cap_bases && n_chunks <= ctx->sk_cap_chunks && n_seqs <= ctx->sk_cap_seqs) return CHAINDP_OK;
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	for (void *b : ctx->sk_allocs) if (b) (void)hipFree(b);
+	ctx->sk_allocs.clear();
+	ctx->sk = {};
+	ctx->sk_cap_bases = ctx->sk_cap_chunks = ctx->sk_cap_seqs = -1;
+	const size_t nb = (size_t)n_bases + (size_t)n_bases / 8 + 1024, nc = (size_t)n_chunks + (size_t)n_chunks / 8 + 64, nq = (size_t)n_seqs + (size_t)n_seqs / 8 + 64;
+	const size_t nt = nb / 256 + 2, nr = (size_t)ctx->cap_reads + 2;
+	size_t scan_items = nc + 1 > nt ? nc + 1 : nt;
+	if (nr > scan_items) scan_items = nr;
+	chaindp::SketchArgs &k = ctx->sk;
+	uint8_t *d_seq = nullptr; int64_t *d_seq_off = nullptr; int32_t *d_chunk_seq = nullptr, *d_seq_chunk0 = nullptr, *d_read_seq0 = nullptr;
+	unsigned long long *d_ybase = nullptr;
+	hipError_t e = sk_alloc(ctx, d_seq, nb + 16);
+	if (e == hipSuccess) e = sk_alloc(ctx, d_seq_off, (nq + 1) * 8);
+	if (e == hipSuccess) e = sk_alloc(ctx, d_chunk_seq, nc * 4);
+	if (e == hipSuccess) e = sk_alloc(ctx, d_seq_chunk0, (nq + 1) * 4);
+	if (e == hipSuccess) e = sk_alloc(ctx, d_read_seq0, nr * 4);
+	if (e == hipSuccess) e = sk_alloc(ctx, d_ybase, nq * 8);
+	if (e == hipSuccess) e = sk_alloc(ctx, k.chunk_push, (nc + 1) * 8);
+	if (e == hipSuccess) e = sk_alloc(ctx, k.chunk_slot, (nc + 1) * 8);
+	if (e == hipSuccess) e = sk_alloc(ctx, k.tile_cnt, nt * 8);
+	if (e == hipSuccess) e = sk_alloc(ctx, k.scan_tmp, (scan_items / 1024 + 4) * 8);
+	if (e == hipSuccess) e = sk_alloc(ctx, k.pcode, nb + 16);
+	if (e == hipSuccess) e = sk_alloc(ctx, k.pstart, nb * 4);
+	if (e == hipSuccess) e = sk_alloc(ctx, k.pend, nb * 4);
+	if (e == hipSuccess) e = sk_alloc(ctx, k.phz, nb * 8);
+	if (e == hipSuccess) e = sk_alloc(ctx, k.sx, nb * 8);
+	if (e == hipSuccess) e = sk_alloc(ctx, k.sy, nb * 8);
+	if (e == hipSuccess) e = sk_alloc(ctx, k.sn, nb + 16);
+	if (e == hipSuccess) e = sk_alloc(ctx, k.slc, nb);
+	if (e == hipSuccess) e = sk_alloc(ctx, k.sseq, nb * 4);
+	if (e == hipSuccess) e = sk_alloc(ctx, k.scnt, nb * 4);
+	if (e != hipSuccess) {
+		(void)hipGetLastError();
+		for (void *b : ctx->sk_allocs) if (b) (void)hipFree(b);
+		ctx->sk_allocs.clear();
+		ctx->sk = {};
+		ctx->err = std::string("sketch buffers for ") + std::to_string((long long)n_bases) + " bases: " + hipGetErrorString(e);
+		return CHAINDP_ERR_CAPACITY;
+	}
+	k.seq = d_seq; k.seq_off = d_seq_off; k.chunk_seq = d_chunk_seq; k.seq_chunk0 = d_seq_chunk0; k.read_seq0 = d_read_seq0; k.seq_ybase = d_ybase;
+	ctx->sk_cap_bases = (int64_t)nb - 16; ctx->sk_cap_chunks = (int64_t)nc; ctx->sk_cap_seqs = (int64_t)nq;
+	return CHAINDP_OK;
+}
+
+extern "C" int chaindp_sketch(chaindp_ctx_t *ctx, int w, int k, int is_hpc, int64_t n_seqs, const int64_t *seq_off, const char *seq,
+                              const int32_t *n_segs_per_read, int64_t *mini_off)
+{
+	if (!ctx) return CHAINDP_ERR_ARG;
+	if (w < 1 || w > 255 || k < 1 || k > 28) { ctx->err = "w must be 1..255 and k 1..28 (sketch.c:84)"; return CHAINDP_ERR_ARG; }
+	if (n_seqs < 0 || !seq_off || seq_off[0] != 0 || !mini_off) { ctx->err = "bad sequence offsets or NULL mini_off"; return CHAINDP_ERR_ARG; }
+	for (int64_t q = 0; q < n_seqs; ++q) {
+		if (seq_off[q + 1] < seq_off[q]) { ctx->err = "sequence offsets must not decrease"; return CHAINDP_ERR_ARG; }
+		if (seq_off[q + 1] - seq_off[q] >= 0x7fffffff) { ctx->err = "a sequence of 2^31-1 bases or more"; return CHAINDP_ERR_CAPACITY; }
+	}
+	const int64_t n_bases = seq_off[n_seqs];
+	if (n_bases > 0 && !seq) { ctx->err = "NULL sequence"; return CHAINDP_ERR_ARG; }
+	if (n_seqs > 0x7ffffff0) { ctx->err = "too many sequences"; return CHAINDP_ERR_CAPACITY; }
+	// reads -> sequences, rid and shift of every sequence (map.c:92-94), lengths of the reads
+	int64_t n_reads = n_seqs;
+	std::vector<int32_t> read_seq0;
+	if (n_segs_per_read) {
+		int64_t q = 0;
+		for (n_reads = 0; q < n_seqs; ++n_reads) {
+			if (n_segs_per_read[n_reads] < 1 || q + n_segs_per_read[n_reads] > n_seqs) { ctx->err = "n_segs_per_read does not add up to n_seqs"; return CHAINDP_ERR_ARG; }
+			read_seq0.push_back((int32_t)q);
+			q += n_segs_per_read[n_reads];
+		}
+		read_seq0.push_back((int32_t)n_seqs);
+	}
+	if (n_reads > ctx->cap_reads) { ctx->err = "batch exceeds the read capacity the context was created with"; return CHAINDP_ERR_CAPACITY; }
+	if (n_bases > ctx->sk_max_bases) { ctx->err = "batch exceeds the bases one chaindp_sketch call takes"; return CHAINDP_ERR_CAPACITY; }
+	std::vector<int32_t> seq_chunk0((size_t)n_seqs + 1), chunk_seq, qlen((size_t)n_reads);
+	std::vector<unsigned long long> ybase((size_t)n_seqs);
+	int64_t n_chunks = 0;
+	for (int64_t r = 0, q = 0; r < n_reads; ++r) {
+		const int64_t q1 = n_segs_per_read ? read_seq0[(size_t)r + 1] : r + 1, first = seq_off[q];
+		if (seq_off[q1] - first > 0x7fffffff) { ctx->err = "a read of more than 2^31-1 bases"; return CHAINDP_ERR_CAPACITY; }
+		qlen[(size_t)r] = (int32_t)(seq_off[q1] - first);
+		for (int64_t rid = 0; q < q1; ++q, ++rid) {
+			const int64_t len = seq_off[q + 1] - seq_off[q], nc = len > 0 ? (len + 255) / 256 : 1;
+			if (n_chunks + nc > 0x7ffffff0) { ctx->err = "too many sequences"; return CHAINDP_ERR_CAPACITY; }
+			seq_chunk0[(size_t)q] = (int32_t)n_chunks;
+			chunk_seq.insert(chunk_seq.end(), (size_t)nc, (int32_t)q);
+			n_chunks += nc;
+			ybase[(size_t)q] = (unsigned long long)rid << 32 | (unsigned long long)(seq_off[q] - first) << 1;
+		}
+	}
+	seq_chunk0[(size_t)n_seqs] = (int32_t)n_chunks;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	int rc = sketch_reserve(ctx, n_bases, n_chunks, n_seqs);
+	if (rc) return rc;
+	if (!ctx->seed_ready && (rc = seed_reserve(ctx, 0)) != CHAINDP_OK) return rc;
+	// A sketch starts a new batch.  Its minimizers go to the buffers of the seed collection, which may have to grow (and with them
+	// the mini_pos[] an earlier batch left), so that batch is dropped here: its downloads are refused or return nothing from now on.
+	ctx->n_reads = 0; ctx->total = 0; ctx->n_seeds = 0; ctx->n_mini_pos = 0; ctx->ran = false; ctx->compact_ready = false; ctx->singles_pending = false;
+	ctx->bot_n_reads = -1; ctx->mp_resident = false; ctx->regs_resident = false; ctx->sk_valid = false;
+	hipStream_t st = ctx->stream;
+	chaindp::SketchArgs a = ctx->sk;
+	a.w = w; a.k = k; a.is_hpc = is_hpc != 0; a.n_seqs = n_seqs; a.n_chunks = n_chunks;
+	if (!n_segs_per_read) a.read_seq0 = nullptr;
+	if (n_bases) HIP_TRY(ctx, hipMemcpyAsync((void*)a.seq, seq, (size_t)n_bases, hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, hipMemcpyAsync((void*)a.seq_off, seq_off, (size_t)(n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, hipMemcpyAsync((void*)a.seq_chunk0, seq_chunk0.data(), (size_t)(n_seqs + 1) * 4, hipMemcpyHostToDevice, st));
+	if (n_chunks) HIP_TRY(ctx, hipMemcpyAsync((void*)a.chunk_seq, chunk_seq.data(), (size_t)n_chunks * 4, hipMemcpyHostToDevice, st));
+	if (n_seqs) HIP_TRY(ctx, hipMemcpyAsync((void*)a.seq_ybase, ybase.data(), (size_t)n_seqs * 8, hipMemcpyHostToDevice, st));
+	if (n_segs_per_read) HIP_TRY(ctx, hipMemcpyAsync((void*)ctx->sk.read_seq0, read_seq0.data(), (size_t)(n_reads + 1) * 4, hipMemcpyHostToDevice, st));
+	hipEvent_t *ev = ctx->sk_ev;
+	if (ctx->prof) for (int i = 0; i < 4; ++i) if (!ev[i]) HIP_TRY(ctx, hipEventCreate(&ev[i]));
+	if (ctx->prof) HIP_TRY(ctx, hipEventRecord(ev[0], st));
+	HIP_TRY(ctx, chaindp::launch_sketch_count(st, a, n_reads, n_bases, (unsigned long long*)ctx->d_mini_off, ctx->d_sk_totals));
+	if (ctx->prof) HIP_TRY(ctx, hipEventRecord(ev[1], st));
+	unsigned long long totals[4] = {0, 0, 0, 0};
+	HIP_TRY(ctx, hipMemcpyAsync(totals, ctx->d_sk_totals, 32, hipMemcpyDeviceToHost, st));
+	ctx->sk_mini_off.assign((size_t)n_reads + 1, 0);
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->sk_mini_off.data(), ctx->d_mini_off, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(ctx, hipStreamSynchronize(st));
+	const int64_t n_mini = (int64_t)totals[2];
+	if (ctx->sk_mini_off[(size_t)n_reads] != n_mini || n_mini < 0 || n_mini > n_bases) { ctx->err = "sketch: inconsistent minimizer counts"; return CHAINDP_ERR_HIP; }
+	if ((rc = seed_reserve(ctx, n_mini, true)) != CHAINDP_OK) return rc;
+	if (ctx->prof) HIP_TRY(ctx, hipEventRecord(ev[2], st));
+	if (n_mini) HIP_TRY(ctx, chaindp::launch_sketch_emit(st, a, n_bases, ctx->d_mini, ctx->seed_cap_mini));
+	if (ctx->prof) HIP_TRY(ctx, hipEventRecord(ev[3], st));
+	HIP_TRY(ctx, hipStreamSynchronize(st));
+	if (ctx->prof) {
+		float m0 = 0, m1 = 0;
+		HIP_TRY(ctx, hipEventElapsedTime(&m0, ev[0], ev[1]));
+		HIP_TRY(ctx, hipEventElapsedTime(&m1, ev[2], ev[3]));
+		ctx->sk_ms += (double)m0 + (double)m1; ctx->sk_calls += 1;
+	}
+	memcpy(mini_off, ctx->sk_mini_off.data(), (size_t)(n_reads + 1) * 8);
+	ctx->sk_qlen.swap(qlen);
+	ctx->sk_n_reads = n_reads; ctx->sk_n_mini = n_mini; ctx->sk_valid = true;
+	return CHAINDP_OK;
+}
+
+extern "C" int chaindp_download_minimizers(chaindp_ctx_t *ctx, chaindp_anchor_t *mini)
+{
+	if (!ctx) return CHAINDP_ERR_ARG;
+	if (!ctx->sk_valid) { ctx->err = "no minimizers of a chaindp_sketch are resident in this context"; return CHAINDP_ERR_ARG; }
+	if (ctx->sk_n_mini > 0 && !mini) { ctx->err = "NULL mini"; return CHAINDP_ERR_ARG; }
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	if (ctx->sk_n_mini) HIP_TRY(ctx, hipMemcpyAsync(mini, ctx->d_mini, (size_t)ctx->sk_n_mini * 16, hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	return CHAINDP_OK;
+}
+
+extern "C" int chaindp_get_sketch_ms(chaindp_ctx_t *ctx, double *ms, int64_t *calls, int reset)
+{
+	if (!ctx) return CHAINDP_ERR_ARG;
+	if (ms) *ms = ctx->sk_ms;
+	if (calls) *calls = ctx->sk_calls;
+	if (reset) { ctx->sk_ms = 0; ctx->sk_calls = 0; }
 	return CHAINDP_OK;
 }
 
@@ -1485,6 +1692,7 @@ extern "C" int chaindp_map_reads(chaindp_ctx_t *ctx, const chaindp_index_t *ix, 
 	if (rc) return rc;
 	if (!opt || !regs_off || regs_cap < 0 || (regs_cap > 0 && !regs) || (n_reads > 0 && !hash)) { ctx->err = "NULL output, hash or opt"; return CHAINDP_ERR_ARG; }
 	if (par->n_segs > 1) { ctx->err = "chaindp_map_reads takes single-segment reads only (n_segs > 1)"; return CHAINDP_ERR_ARG; }
+	if (!mini && !mini_off && !qlen && ctx->sk_valid && n_reads == ctx->sk_n_reads) qlen = ctx->sk_qlen.data();   // the resident sketch's (checked below)
 	// the stages of chaindp_map_batch, with the hits left in HBM, then chain_post on them
 	if ((rc = collect_seeds_impl(ctx, ix, flag, max_occ, n_reads, mini_off, mini, nullptr, bid, qlen, nullptr, nullptr, rep_len, nullptr)) != CHAINDP_OK) return rc;
 	if (n_anchors) *n_anchors = ctx->total;
@@ -1493,4 +1701,20 @@ extern "C" int chaindp_map_reads(chaindp_ctx_t *ctx, const chaindp_index_t *ix, 
 	if ((rc = chaindp_backtrack(ctx, par, min_cnt, c_off.data(), nullptr, b_off.data(), nullptr)) != CHAINDP_OK) return rc;
 	if ((rc = gen_regs_impl(ctx, hash, qlen, nullptr, false)) != CHAINDP_OK) return rc;
 	return chaindp_chain_post(ctx, opt, nullptr, nullptr, ref_len, n_ref, nullptr, nullptr, regs_off, regs, regs_cap, nullptr, nullptr);
+}
+
+extern "C" int chaindp_map_seqs(chaindp_ctx_t *ctx, const chaindp_index_t *ix, int w, int k, int is_hpc, int flag, int max_occ, const chaindp_params_t *par,
+                                int min_cnt, const chaindp_post_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seq, const uint32_t *bid,
+                                const uint32_t *hash, const int32_t *ref_len, int32_t n_ref, int64_t *regs_off, chaindp_reg_t *regs, int64_t regs_cap,
+                                int32_t *rep_len, int64_t *n_anchors)
+{
+	if (!ctx) return CHAINDP_ERR_ARG;
+	int rc = check_params(ctx, par);
+	if (rc) return rc;
+	if (!opt || !regs_off || regs_cap < 0 || (regs_cap > 0 && !regs) || (n_reads > 0 && (!hash || !bid))) { ctx->err = "NULL output, bid, hash or opt"; return CHAINDP_ERR_ARG; }
+	if (!ix || ix->device != ctx->device) { ctx->err = "index image missing or on another device"; return CHAINDP_ERR_ARG; }
+	std::vector<int64_t> mini_off((size_t)(n_reads > 0 ? n_reads + 1 : 1));
+	if ((rc = chaindp_sketch(ctx, w, k, is_hpc, n_reads, seq_off, seq, nullptr, mini_off.data())) != CHAINDP_OK) return rc;
+	return chaindp_map_reads(ctx, ix, flag, max_occ, par, min_cnt, opt, n_reads, nullptr, nullptr, bid, nullptr, hash, ref_len, n_ref, regs_off, regs,
+	                         regs_cap, rep_len, n_anchors);
 }

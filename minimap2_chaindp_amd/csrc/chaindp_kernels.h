@@ -216,6 +216,33 @@ hipError_t launch_seed_expand_sort(hipStream_t st, const SeedIndex &ix, int flag
 // The host picks the largest max_n (<= 8192) and max_n2 that fit the device's LDS per workgroup.
 size_t seed_sort_lds_bytes(int max_n, int workers, int coop);
 
+// mm_sketch for a batch (chaindp_sketch.hip).  The host lists the 256-base chunks of every sequence (an empty sequence gets one
+// empty chunk): chunk_seq[n_chunks], seq_chunk0[n_seqs + 1]; seq_ybase[q] = rid << 32 | shift << 1 of collect_minimizers (map.c:92-94);
+// read_seq0[n_reads + 1] = first sequence of every read, NULL when every read is one sequence.  Everything else is scratch, sized by
+// the batch's bases (a push and a slot need a base each) and by its chunks.
+struct SketchArgs {
+	int w, k, is_hpc;
+	int64_t n_seqs, n_chunks;
+	const uint8_t *seq;
+	const int64_t *seq_off;
+	const int32_t *chunk_seq, *seq_chunk0, *read_seq0;
+	const unsigned long long *seq_ybase;
+	unsigned long long *chunk_push, *chunk_slot;   // n_chunks + 1: pushes / slots per chunk, scanned in place
+	unsigned long long *tile_cnt;                   // minimizers per 256-slot tile, scanned in place
+	unsigned long long *scan_tmp;
+	uint8_t *pcode; int32_t *pstart, *pend;         // per push: code, first and last base of its run (position in the sequence)
+	unsigned long long *phz;                        // per push: hash << 1 | strand, all ones for a symmetric k-mer
+	unsigned long long *sx, *sy;                    // per slot: the window entry
+	uint8_t *sn, *slc;                              // per slot: ambiguous base; 0 / 1 / 2 for l < w+k-1, == w+k-1, >= w+k
+	int32_t *sseq;                                  // per slot: its sequence
+	uint32_t *scnt;                                 // per slot: minimizers it pushes (at most 2w + 1) | distance to the one it pushes << 16
+};
+// phase 1: everything up to the counts -- d_mini_off[n_reads + 1] and d_totals[4] = pushes, slots, minimizers, unused; the host reads the total (the minimizer buffer may have to grow) and runs
+// phase 2: the minimizers, in order, into d_mini (room for mini_cap; nothing is written past it).
+hipError_t launch_sketch_count(hipStream_t st, const SketchArgs &a, int64_t n_reads, int64_t n_bases, unsigned long long *d_mini_off,
+                               unsigned long long *d_totals);
+hipError_t launch_sketch_emit(hipStream_t st, const SketchArgs &a, int64_t n_bases, void *d_mini, int64_t mini_cap);
+
 // zero-copy movement between device-visible (pinned) host buffers and HBM: chaindp_io.hip
 hipError_t launch_gather_reads(hipStream_t st, int64_t n_reads, const int64_t *d_off, const void *const *d_src, void *d_a);
 hipError_t launch_scatter_seeds(hipStream_t st, int64_t n_reads, const int64_t *d_seeds_off, void *const *d_dst, const void *d_seeds);
