@@ -23,6 +23,32 @@ namespace chaindp {
 typedef uint32_t tw_u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t tw_u32x4 __attribute__((ext_vector_type(4)));
 
+// The kernel's argument struct where it is used, not where the kernel starts: a pointer to the kernel-argument segment (the struct
+// is the kernel's only parameter: byte 0 of the segment), so that a field is one s_load through the scalar cache at its point of
+// use.  The empty asm hides where the pointer comes from: the compiler can neither hoist these loads above the pass loops nor keep
+// the by-value struct's fields in scalar registers through them -- it spilled those into vector lanes and took them back a
+// sixteen-register tuple at a time, a v_readlane each.  Take a new one (TW_KARGS) in every rarely run region.
+#if defined(__HIP_DEVICE_COMPILE__)
+template <class T> __device__ __forceinline__ const __attribute__((address_space(4))) T *tw_kargs(const T &)
+{
+	const __attribute__((address_space(4))) T *k = (const __attribute__((address_space(4))) T*)__builtin_amdgcn_kernarg_segment_ptr();
+	asm volatile("" : "+s"(k));
+	return k;
+}
+#define TW_KARGS(g) tw_kargs(g)
+// element of type T at byte `off` (32 bits, per lane, unsigned) behind the wave-uniform global pointer p: the scalar base + vector
+// offset form of the global instructions -- no 64-bit address arithmetic in vector registers
+#define TW_AT(T, p, off) (*(__attribute__((address_space(1))) T*)((__attribute__((address_space(1))) char*)(p) + (uint32_t)(off)))
+#else
+#define TW_KARGS(g) (&(g))
+#define TW_AT(T, p, off) (*(T*)((char*)(p) + (uint32_t)(off)))
+#endif
+// atomicMin (device scope, result unused) on an element addressed by TW_AT
+template <class P> __device__ __forceinline__ void tw_atomic_min(P *p, int v)
+{
+	(void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 __device__ __forceinline__ tw_u32x2 tw_ld64(uint32_t a) { return *TW_LDS(const tw_u32x2, a); }
 __device__ __forceinline__ int tw_ld32(uint32_t a) { return *TW_LDS(const int, a); }
 __device__ __forceinline__ int tw_ld_i8(uint32_t a) { return (int)*TW_LDS(const signed char, a); }

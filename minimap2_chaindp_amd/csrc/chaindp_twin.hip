@@ -163,6 +163,9 @@ __device__ __forceinline__ uint64_t tw_below_first(uint64_t m, uint64_t b)
 	return m & ((uint64_t)khi << 32 | klo);
 }
 
+// a lane's byte offset for TW_AT, pinned to the block that uses it: instruction selection works a block at a time and takes the
+// scalar base + 32-bit vector offset form only where it sees the offset's zero-extension, which the compiler otherwise hoists
+__device__ __forceinline__ uint32_t tw_here(uint32_t x) { TW_VREG(x); return x; }
 #define TW_HI31 0x8000000080000000ull
 
 // per half: the bits of a above the lowest set bit of b, for disjoint a and b (b's lowest bit and all above it are set in -b; none
@@ -315,24 +318,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 	if (!SAMEGAP) TW_VREG(c_dqoff);
 	TW_VREG(c_min); TW_VREG(c_bwl); TW_VREG(c_cbwl);
 
-	const uint64_t maxx = (uint64_t)(int64_t)g.par.max_dist_x;
 	// (uniform) which kernel takes the batch: k_chain_quad has written 1 before this kernel starts; the one-table layout takes
 	// batches whose units share one table key and writes 2, which the two-table layout, launched behind it, then finds
 	const uint32_t route = *g.route;
 	if (ONE_LUT ? route == 1u || g.key_range[0] != g.key_range[1] || g.two_tables : route == 1u || route == 2u) return;
-	const int64_t n_units = (int64_t)(uint32_t)g.counters[0];
-	// the kernel's 32-bit differences (and the signed window test) are exact while 129 * (max_dist_x + 1) < 2^31
+	const uint32_t n_units = (uint32_t)g.counters[0];                // (32 bits: one scalar register through the pass loops)
 	// Units of a few thousand anchors (map-ont shape) are few and each is a long serial chain: two of them side by side gain
 	// nothing and their scans need the second chunk for one anchor in three.  Such batches go to k_chain_units as a whole.
 	const int64_t n_single = (int64_t)(g.counters[0] >> 32);
-	const bool short_units = (g.total - n_single) <= 512 * n_units;
+	const bool short_units = (g.total - n_single) <= 512 * (int64_t)n_units;
 	if (!short_units) {                                            // (uniform: every block leaves; one of them says so)
 		if (blockIdx.x == 0 && lane == 0) *g.left_cnt = 0xffffffffu;
 		return;
 	}
 	if (blockIdx.x == 0 && lane == 0) *g.route = ONE_LUT ? 2u : 3u;
-	const bool params_ok = g.lut != nullptr && !g.par.is_cdna && g.par.max_dist_x >= 1 && g.par.max_dist_y >= 0 &&
-	                       ((uint64_t)(int64_t)g.par.max_dist_x + 1) * 129ull < (1ull << 31) && g.par.bw + 1 <= (int)TW_LUT_BYTES && g.force_left != 1;
+	// (whether the parameters are this kernel's at all is asked where a unit is picked up: params_ok in service())
 
 	TwinHot u;
 	u.S = 0; u.m4 = 0; u.pc = L::HAS_XQ ? curbase : 0u; u.pend = u.pc;
@@ -346,13 +346,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 	// last sixteen units per half: the list is longest first, every half works on units of the same length at any time, and the
 	// halves run out of work within one grab of each other -- eight units of 140 anchors were 0.4 ms, 0.2 ms of idle tail on average
 	// behind a 3 ms kernel.  (Smaller grabs all along cost more than they save: same-address atomics.)
-	const uint32_t xcd = blockIdx.x & 7u;
-	const uint32_t n_halves = 2u * gridDim.x;
 #ifndef TW_END_UNITS
 #define TW_END_UNITS 16u                // units per half that are dealt in small pieces at the end of the list
 #define TW_PIECE 1u                     // ... this many at a time (measured on the 76 M-anchor shard: 16 / 1: 2.86 ms, 16 / 2: 2.88, 24 / 1: 2.88, 32 / 2: 2.90, 8 / 2: 2.95; one counter, 8 at a time all along: 3.04)
 #endif
-	const uint32_t U1 = n_units > (long long)TW_END_UNITS * n_halves ? ((uint32_t)n_units - TW_END_UNITS * n_halves) & ~(8u * TW_QCH - 1u) : 0u;
+	// (the queue's geometry stays worked out here, three scalar registers kept for the grabs: worked out at each grab instead, the
+	// register allocation of every instantiation tips into VGPR spills)
+	const uint32_t xcd = blockIdx.x & 7u;
+	const uint64_t end_units = (uint64_t)TW_END_UNITS * 2u * gridDim.x;      // TW_END_UNITS per half
+	const uint32_t U1 = n_units > end_units ? (n_units - (uint32_t)end_units) & ~(8u * TW_QCH - 1u) : 0u;
 	const uint32_t G1k = U1 / (8u * TW_QCH);                             // grabs of whole chunks per counter
 	auto grab = [&](uint32_t p, uint32_t &nx, uint32_t &ne) {
 		if (p < G1k) { nx = (8u * p + xcd) * TW_QCH; ne = nx + TW_QCH; }
@@ -388,6 +390,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 	// Once per 64 anchors and half.  Where the layout prefetches (PF), the next tile and a successor unit's first tile are already in
 	// registers, requested a tile of passes ago.
 	auto service = [&](uint64_t svc) {
+		const auto kp = TW_KARGS(g);                                     // the arguments, read where they are used (chaindp_lanes.h)
+		// the lane number, and what the service derives from it (ring and table addresses, byte offsets into a tile of the global
+		// arrays: 4, 16 and 1 bytes an anchor), from a value the compiler cannot trace: it would work them out once and keep them in
+		// vector registers through the pass loops, which have none to spare
+		uint32_t ln = (uint32_t)threadIdx.x;
+		TW_VREG(ln);
+		const int lane = (int)ln;                                        // (hides the kernel's `lane`)
 #if defined(__HIP_DEVICE_COMPILE__)
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // (whatever is outstanding was issued a tile of passes ago: no wait in practice)
 #endif
@@ -417,15 +426,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 			const int tile_prev = c_tile0, rel0_prev = c_rel0;
 			const int64_t base_prev = c_base;
 			bool live = true;
+			// the parameters are this kernel's (else every unit is handed over).  The kernel's 32-bit differences (and the signed window
+			// test) are exact while 129 * (max_dist_x + 1) < 2^31.  Asked where a unit is picked up, from the kernel arguments.
+			auto params_ok = [&]() -> bool {
+				return kp->lut != nullptr && !kp->par.is_cdna && kp->par.max_dist_x >= 1 && kp->par.max_dist_y >= 0 && kp->par.n_segs <= 1 &&
+				       ((uint64_t)(int64_t)kp->par.max_dist_x + 1) * 129ull < (1ull << 31) && kp->par.bw + 1 <= (int)TW_LUT_BYTES && kp->force_left != 1;
+			};
 			// The half's next unit (PF: and the one after it), in case this call needs them -- the unit ends here, or (PF) with the tile
 			// taken now, and its successor's first tile is then requested a tile ahead: records and UnitAux through the scalar cache,
 			// issued before the work below and read after it.
 			const uint32_t nx0 = (uint32_t)c_next, ne0 = (uint32_t)((uint64_t)c_next >> 32);
 			tw_u32x4 rec0 = {0u, 0u, 0u, 0u}, aux0 = {0u, 0u, 0u, 0u}, rec1 = {0u, 0u, 0u, 0u};
-			const bool rec0_ok = nx0 < ne0 && (int64_t)nx0 < n_units;       // (whenever they are known: a unit can end before its bound says so)
-			const bool rec1_ok = PF && rec0_ok && nx0 + 1u < ne0 && (int64_t)nx0 + 1 < n_units;
-			if (rec0_ok) { rec0 = *TW_CONST(tw_u32x4, g.units + nx0); aux0 = *TW_CONST(tw_u32x4, g.aux + nx0); }
-			if (rec1_ok) rec1 = *TW_CONST(tw_u32x4, g.units + nx0 + 1u);
+			const bool rec0_ok = nx0 < ne0 && nx0 < n_units;       // (whenever they are known: a unit can end before its bound says so)
+			const bool rec1_ok = PF && rec0_ok && nx0 + 1u < ne0 && (uint64_t)nx0 + 1u < n_units;
+			if (rec0_ok) { rec0 = *TW_CONST(tw_u32x4, kp->units + nx0); aux0 = *TW_CONST(tw_u32x4, kp->aux + nx0); }
+			if (rec1_ok) rec1 = *TW_CONST(tw_u32x4, kp->units + nx0 + 1u);
 
 			// takes a tile's anchors (one per lane, raw mm128_t) into the half's LDS: where the unit ends (first gap > max_dist_x,
 			// chain.c:252), XY ring (the anchors as predecessors and as the current anchor), SP.  Returns the anchors the tile holds
@@ -439,7 +454,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 					if (lane == 0) { lo = (uint32_t)c_xcarry; hi = (uint32_t)(c_xcarry >> 32); }
 					xp = (uint64_t)hi << 32 | lo;
 				}
-				const bool stop = !have || (i_lane > 0 && an_x - xp > maxx);
+				const bool stop = !have || (i_lane > 0 && an_x - xp > (uint64_t)(int64_t)kp->par.max_dist_x);
 				const uint64_t stop_m = __builtin_amdgcn_ballot_w64(stop);
 				const int cnt = stop_m ? __builtin_ctzll(stop_m) : TW_TILE;
 				c_xcarry = readlane_u64(an_x, 63);
@@ -457,14 +472,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 					// first_child[] starts at "none" for every anchor the kernel takes in: stored here, a whole tile of passes before the
 					// tile's flush (or any later one) lowers it with atomics -- and service() waits for the wave's outstanding memory
 					// operations when it starts, so those atomics come after this store in memory as well.  No batch-wide memset.
-					g.first_child[c_base + i_lane] = NO_CHILD;
+					TW_AT(int32_t, kp->first_child + (c_base + c_tile0), tw_here(ln << 2)) = NO_CHILD;
 				}
 				wave_mem_fence();
 				if constexpr (PF) {
 					// the tile after this one: the load is issued now and read at the half's next service, 64 anchors of work later
 					if (cnt == TW_TILE && c_tile0 + TW_TILE < c_room) {        // (else: the unit ends with this tile; the registers are for its successor)
 						uint64_t rx = 0, ry = 0;
-						if (i_lane + TW_TILE < c_room) { const ulonglong2 t = g.a[c_base + i_lane + TW_TILE]; rx = t.x; ry = t.y; }
+						if (i_lane + TW_TILE < c_room) { const ulonglong2 t = TW_AT(const ulonglong2, kp->a + (c_base + c_tile0 + TW_TILE), tw_here(ln << 4)); rx = t.x; ry = t.y; }
 						if (hs) { nx1_x = rx; nx1_y = ry; pfu1 = -1; } else { nx0_x = rx; nx0_y = ry; pfu0 = -1; }
 					}
 				}
@@ -473,13 +488,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 
 			// ---- the unit goes on?
 			bool goes_on = cnt_prev == TW_TILE && c_tile0 + TW_TILE < c_room;
-			if (goes_on && (slow_h * 8 > c_tile0 + TW_TILE || g.force_left == 2)) {
+			if (goes_on && (slow_h * 8 > c_tile0 + TW_TILE || kp->force_left == 2)) {
 				// a unit that keeps needing second chunks (more than one anchor in eight) is cheaper in k_chain_units: hand the rest of
 				// it over.  The tiles up to the one flushed below are done: k_chain_units goes on behind them (the count rides in the
 				// high word of the start; force_left == 2 is the tests' way to send every unit down this road)
 				if (lane == 0) {
 					Unit un; un.start = (int64_t)((uint64_t)c_base | (uint64_t)(uint32_t)(c_tile0 + TW_TILE) << 32); un.read = c_read; un.len = c_room;
-					g.left[atomicAdd(g.left_cnt, 1u)] = un;
+					kp->left[atomicAdd(kp->left_cnt, 1u)] = un;
 				}
 				goes_on = false;
 			}
@@ -488,7 +503,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 				c_tile0 += TW_TILE;
 				uint64_t nt_x = 0, nt_y = 0;
 				if constexpr (PF) { nt_x = hs ? nx1_x : nx0_x; nt_y = hs ? nx1_y : nx0_y; }
-				else if (c_tile0 + lane < c_room) { const ulonglong2 t = g.a[c_base + c_tile0 + lane]; nt_x = t.x; nt_y = t.y; }
+				else if (c_tile0 + lane < c_room) { const ulonglong2 t = TW_AT(const ulonglong2, kp->a + (c_base + c_tile0), tw_here(ln << 4)); nt_x = t.x; nt_y = t.y; }
 				if (take_tile(nt_x, nt_y) == 0) goes_on = false;     // (0: the unit ended exactly on the boundary)
 			}
 			TW_STAMP_B(if (g.stamp) st_take += (unsigned int)(TW_NOW() - th0);)
@@ -497,7 +512,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 			if (cnt_prev > 0) {
 				const int i_lane = tile_prev + lane;                         // this lane's anchor of the finished tile
 				const bool have = lane < cnt_prev;
-				const int64_t gi = base_prev + i_lane;
+				// the tile's place in the five output arrays: a scalar base each (64-bit scalar arithmetic) and one lane offset, 4 * lane
+				// (flags: lane) -- relative to the tile, so that it fits 32 bits whatever the batch holds
+				const int64_t g0 = base_prev + tile_prev;
+				int32_t *const f0 = kp->f + g0, *const p0 = kp->p + g0, *const v0 = kp->v + g0;
+				uint8_t *const fl0 = kp->flags + g0;
+				// a predecessor is at most TW_RING anchors behind its anchor: first_child from TW_RING anchors before the tile
+				int32_t *const fc0 = kp->first_child + (g0 - TW_RING);
+				const int min_sc = kp->par.min_sc;
 				int fi = 0, p4 = -4;
 				if (have) {
 					const tw_u32x2 pf = tw_ld64((((uint32_t)i_lane & 63u) << 4 | (uint32_t)hs << 3) + TW_PF);
@@ -520,7 +542,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 					const int pp = __builtin_amdgcn_ds_bpermute(src, ptr);
 					if (ptr >= tile_prev) { val = max(val, pv); ptr = pp; }
 				}
-				const bool self = val >= g.par.min_sc || pi >= 0;            // emitted at its own step (chain.c:304)
+				const bool self = val >= min_sc || pi >= 0;            // emitted at its own step (chain.c:304)
 				// is the predecessor emitted at its own step?  in-tile predecessors: ask their lane
 				const int srcp = (pi >= tile_prev ? pi - tile_prev : lane) << 2;
 				const int pself_in = __builtin_amdgcn_ds_bpermute(srcp, self ? 1 : 0);
@@ -530,12 +552,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 				wave_mem_fence();
 				// (first_child[] of the tile's anchors is NO_CHILD since the tile was taken in)
 				if (have) {
-					g.f[gi] = fi;
-					g.p[gi] = pi < 0 ? -1 : pi + rel0_prev;
-					g.v[gi] = val;
+					const uint32_t l4 = tw_here(ln << 2);
+					TW_AT(int32_t, f0, l4) = fi;
+					TW_AT(int32_t, p0, l4) = pi < 0 ? -1 : pi + rel0_prev;
+					TW_AT(int32_t, v0, l4) = val;
 					int maybe_first = 0;
-					if (pi >= 0 && !pred_self) { atomicMin(&g.first_child[base_prev + pi], rel0_prev + i_lane); maybe_first = 4; }
-					g.flags[gi] = (uint8_t)((self ? 2 : 0) | maybe_first | (val >= g.par.min_sc ? 8 : 0) | (fi < val ? 16 : 0));
+					if (pi >= 0 && !pred_self) {
+						tw_atomic_min(&TW_AT(int32_t, fc0, tw_here((uint32_t)(pi - tile_prev + TW_RING) << 2)), rel0_prev + i_lane);
+						maybe_first = 4;
+					}
+					TW_AT(uint8_t, fl0, tw_here(ln)) = (uint8_t)((self ? 2 : 0) | maybe_first | (val >= min_sc ? 8 : 0) | (fi < val ? 16 : 0));
 				}
 			}
 			TW_STAMP_A(if (g.stamp) st_flush += (unsigned int)(TW_NOW() - tf0);)
@@ -551,26 +577,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 					// the chunk is used up: the counter's next grab (the list is longest first, so the two halves of a wave, and all
 					// waves, work on units of similar length at any time and run out of work together)
 					uint32_t q0 = 0;
-					if (lane == 0) q0 = atomicAdd(g.queue + 64u * xcd, 1u);
+					if (lane == 0) q0 = atomicAdd(kp->queue + 64u * xcd, 1u);
 					grab(TW_UNI(q0), nx, ne);
 					have_rec = false;
 				}
-				if ((int64_t)nx >= n_units) {
+				if (nx >= n_units) {
 					c_next = (int64_t)((uint64_t)ne << 32 | nx); live = false;
 					if constexpr (L::HAS_XQ) { u.pc = TW_SEL(hm, curb, u.pc); u.pend = TW_SEL(hm, curb, u.pend); }
 					else u.pend = TW_SEL(hm, 0u, u.pend);
 					break;
 				}
 				TW_STAMP_C(const unsigned long long tc0 = g.stamp ? TW_NOW() : 0;)
-				if (!have_rec) { rec0 = *TW_CONST(tw_u32x4, g.units + nx); aux0 = *TW_CONST(tw_u32x4, g.aux + nx); }
+				if (!have_rec) { rec0 = *TW_CONST(tw_u32x4, kp->units + nx); aux0 = *TW_CONST(tw_u32x4, kp->aux + nx); }
 				have_rec = false;
 				TW_STAMP_C(if (g.stamp) { asm volatile("" :: "s"(rec0.x), "s"(aux0.x)); st_head += (unsigned int)(TW_NOW() - tc0); })
 				c_next = (int64_t)((uint64_t)ne << 32 | (nx + 1u));
 				Unit un;
 				un.start = (int64_t)((uint64_t)rec0.y << 32 | rec0.x); un.read = (int32_t)rec0.z; un.len = (int32_t)rec0.w;
-				if (!params_ok || (aux0.z & 1u) || g.par.n_segs > 1 || (ONE_LUT && cur_key_now != 0xffffffffu && aux0.y != cur_key_now)) {
+				if (!params_ok() || (aux0.z & 1u) || (ONE_LUT && cur_key_now != 0xffffffffu && aux0.y != cur_key_now)) {
 					// not for this kernel: hand the unit over (the key test, one table per wave, cannot fail: key_range)
-					if (lane == 0) g.left[atomicAdd(g.left_cnt, 1u)] = un;
+					if (lane == 0) kp->left[atomicAdd(kp->left_cnt, 1u)] = un;
 					continue;
 				}
 				c_base = un.start; c_rel0 = (int)aux0.x; c_room = un.len; c_read = un.read; c_tile0 = 0;
@@ -579,7 +605,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 				TW_STAMP_C(const unsigned long long tc1 = g.stamp ? TW_NOW() : 0;)
 				TW_STAMP_C(if (g.stamp && PF && (hs ? pfu1 : pfu0) == (int32_t)c_base) ++st_n_unit;)
 				if (PF && (hs ? pfu1 : pfu0) == (int32_t)c_base) { tl_x = hs ? nx1_x : nx0_x; tl_y = hs ? nx1_y : nx0_y; }
-				else if (lane < c_room) { const ulonglong2 t = g.a[c_base + lane]; tl_x = t.x; tl_y = t.y; }
+				else if (lane < c_room) { const ulonglong2 t = TW_AT(const ulonglong2, kp->a + c_base, tw_here(ln << 4)); tl_x = t.x; tl_y = t.y; }
 				if constexpr (PF) { if (hs) pfu1 = -1; else pfu0 = -1; }
 				TW_STAMP_C(if (g.stamp) { asm volatile("" :: "v"(tl_x), "v"(tl_y)); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); st_take += (unsigned int)(TW_NOW() - tc1); })
 				TW_STAMP_C(const unsigned long long tc2 = g.stamp ? TW_NOW() : 0;)
@@ -587,8 +613,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 				// the table in place is that of a read with the same avg_qspan
 				wave_mem_fence();
 				if (aux0.y != cur_key_now) {
-					const uint2 *src = (const uint2*)(g.lut + (int64_t)c_read * g.lut_stride);
-					for (int k = lane; k * 4 <= g.par.bw; k += 64) {           // lut_stride is a multiple of 8 entries: whole uint2 loads
+					const uint2 *src = (const uint2*)(kp->lut + (int64_t)c_read * kp->lut_stride);
+					for (int k = lane; k * 4 <= kp->par.bw; k += 64) {           // lut_stride is a multiple of 8 entries: whole uint2 loads
 						const uint2 t = src[k];
 						const uint32_t w = (t.x & 0xffu) | (t.x >> 8 & 0xff00u) | (t.y << 16 & 0xff0000u) | (t.y << 8 & 0xff000000u);
 						tw_st32(lutb + ((uint32_t)k << 2), (int)w);
@@ -596,7 +622,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 					cur_key_now = aux0.y;
 					if (lane == 0) tw_st32(keya, (int)cur_key_now);
 				}
-				const uint32_t x_none = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tl_x, 0) - (uint32_t)maxx - 1u;   // "no anchor here" (x+1 encoding)
+				const uint32_t x_none = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tl_x, 0) - (uint32_t)kp->par.max_dist_x - 1u;   // "no anchor here" (x+1 encoding)
 				for (int k = lane; k < 128; k += 64) tw_st64(((uint32_t)k << 4 | (uint32_t)hs << 3) + TW_XY, x_none, 0u);
 				for (int k = lane; k < 65; k += 64) tw_st32(mkb + ((uint32_t)k << 2), -1);
 				wave_mem_fence();
@@ -609,12 +635,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 			if (PF && live) {
 				const int cnt_now = tile_cnt();
 				const uint32_t nxn = (uint32_t)c_next, nen = (uint32_t)((uint64_t)c_next >> 32);
-				if (!(cnt_now == TW_TILE && c_tile0 + TW_TILE < c_room) && (hs ? pfu1 : pfu0) < 0 && nxn < nen && (int64_t)nxn < n_units &&
+				if (!(cnt_now == TW_TILE && c_tile0 + TW_TILE < c_room) && (hs ? pfu1 : pfu0) < 0 && nxn < nen && nxn < n_units &&
 				    ((nxn == nx0 && rec0_ok && !rec0_used) || (nxn == nx0 + 1u && rec1_ok))) {
 					const tw_u32x4 rn = nxn == nx0 ? rec0 : rec1;            // (nxn == nx0: the loop above did not run, rec0 is untouched)
-					const int32_t st = (int32_t)rn.x, ln = (int32_t)rn.w;
+					const int32_t st = (int32_t)rn.x, len = (int32_t)rn.w;
 					uint64_t rx = 0, ry = 0;
-					if (lane < ln) { const ulonglong2 t = g.a[(int64_t)st + lane]; rx = t.x; ry = t.y; }
+					if (lane < len) { const ulonglong2 t = TW_AT(const ulonglong2, kp->a + (int64_t)st, tw_here(ln << 4)); rx = t.x; ry = t.y; }
 					if (hs) { nx1_x = rx; nx1_y = ry; pfu1 = st; } else { nx0_x = rx; nx0_y = ry; pfu0 = st; }
 				}
 			}
@@ -659,12 +685,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 		}
 		contm = ~D & ~giveup & live_m;
 		if (__builtin_expect(giveup != 0, 0)) {
+			const auto kp = TW_KARGS(g);
 			if (__builtin_amdgcn_inverse_ballot_w64(giveup)) {
 				wave_mem_fence();
 				if (hl == 0) {
 					const TwinCold c = TW_COLD;
 					Unit un; un.start = (int64_t)((uint64_t)c.base | (uint64_t)(uint32_t)c.tile0 << 32); un.read = c.read; un.len = c.room;
-					g.left[atomicAdd(g.left_cnt, 1u)] = un;                  // k_chain_units goes on from the tile this scan is in (the tiles
+					kp->left[atomicAdd(kp->left_cnt, 1u)] = un;                  // k_chain_units goes on from the tile this scan is in (the tiles
 					                                                         // before it are flushed).  The unit is over for this kernel: an empty tile ...
 				}
 				u.pc = curbase; u.pend = L::HAS_XQ ? curbase : 0u;            // ... has nothing to flush and cannot go on: service() picks the half's next unit
@@ -703,17 +730,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 					const int n0 = (int)(TW_UNI(__builtin_amdgcn_readlane((int)u.pend, 0)) - TW_UNI(__builtin_amdgcn_readlane((int)u.pc, 0))) >> 3;
 					const int n1 = (int)(TW_UNI(__builtin_amdgcn_readlane((int)u.pend, 32)) - TW_UNI(__builtin_amdgcn_readlane((int)u.pc, 32))) >> 3;
 					npass = max(min(n0, n1), 1);
-				} else {
+				} else if constexpr (!SAMEGAP) {
+					// (the seven-wave instantiation keeps the scalar form of the block below: with the vector form its register
+					// allocation spills four more scalar registers in the service)
 					const uint32_t m0 = TW_UNI(__builtin_amdgcn_readlane((int)u.m4, 0)), m1 = TW_UNI(__builtin_amdgcn_readlane((int)u.m4, 32));
 					const int n0 = (int)(TW_UNI(__builtin_amdgcn_readlane((int)u.pend, 0)) - m0) >> 2;
 					const int n1 = (int)(TW_UNI(__builtin_amdgcn_readlane((int)u.pend, 32)) - m1) >> 2;
 					npass = max(min(n0, n1), 1);
-					// a half whose anchor is one of its unit's first 32 (i <= 31) has its lane 31 on a slot from before the unit, which
-					// fails the window test: its scan is complete whether it breaks or not.  Such a half counts as having 32 B lanes (E)
-					// for the passes until its i reaches 32, and the stretch of passes ends there (the outer loop sets E again).
 					const int e0 = 31 - ((int)(m0 - L::MK) >> 2), e1 = 31 - ((int)(m1 - L::MK - TW_MK_HALF) >> 2);   // 32 - i (m4 = 4 (i - 1) + mark base)
 					if (e0 > 0) { E |= 0x00000000ffffffffull; npass = min(npass, e0); }
 					if (e1 > 0) { E |= 0xffffffff00000000ull; npass = min(npass, e1); }
+				} else {
+					// Passes until either half's tile ends (at least one), worked out per half in its own lanes (plain two-operand VALU) and
+					// read from one lane of each: as scalar code on four v_readlane it was 27 scalar instructions at every entry of this
+					// loop, and the loop is entered at every tile and twice more per unit.
+					// A half whose anchor is one of its unit's first 32 (i <= 31) has its lane 31 on a slot from before the unit, which
+					// fails the window test: its scan is complete whether it breaks or not.  Such a half counts as having 32 B lanes (E)
+					// for the passes until its i reaches 32, and the stretch of passes ends there (the outer loop sets E again).
+					const uint32_t tm1 = (uint32_t)max(((int)(u.pend - u.m4) >> 2) - 1, 0);         // passes left in the tile, minus one
+					const uint32_t em1 = 30u - (uint32_t)((int)(u.m4 - c_mkbase) >> 2);              // 32 - i - 1 (m4 = 4 (i - 1) + mark base): above 31 for i >= 32
+					const uint32_t nm1 = min(tm1, em1);
+					E = TW_ULT(em1, 32u);
+					npass = (int)min(TW_UNI(__builtin_amdgcn_readlane((int)nm1, 0)), TW_UNI(__builtin_amdgcn_readlane((int)nm1, 32))) + 1;
 				}
 				const uint32_t ms0 = (uint32_t)max(g.par.max_skip, 0);           // a half's scan breaks in this chunk iff it has more B lanes
 				uint32_t P = (uint32_t)npass + ms0;                              // passes left + ms0 (npass <= 64: no wrap)
