@@ -275,6 +275,55 @@ int chaindp_map_seqs(chaindp_ctx_t *ctx, const chaindp_index_t *idx, int w, int 
                      int min_cnt, const chaindp_post_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seq, const uint32_t *bid,
                      const uint32_t *hash, const int32_t *ref_len, int32_t n_ref, int64_t *regs_off, chaindp_reg_t *regs, int64_t regs_cap,
                      int32_t *rep_len, int64_t *n_anchors);
+/* ---- reads of several segments (paired reads): fragments in, per-segment hits out ---------------------------------------------
+ * read_result_handle for n_segs > 1 without MM_F_CIGAR (map.c:870-890) on the hits the last chaindp_gen_regs left in HBM, for a batch
+ * whose reads own 1..255 segments each (MM_MAX_SEG); segment q is the q-th sequence of the batch (n_seqs = the sum of the reads'
+ * segments).  chaindp_chain_post, chaindp_map_reads and chaindp_map_seqs keep refusing such batches.
+ *   a read of one segment (an orphan)   exactly chaindp_chain_post's steps: the same bytes, div included
+ *   a read of several segments          chain_post with mm_select_sub_multi (pe.c:6-43; its max_gap_ref is the max_dist_x of the
+ *                                       chaindp_params_t the batch was run with, map.c:361-366) in the place of mm_select_sub, and
+ *                                       mm_join_long unless opt->flag excludes it (map.c:244); mm_seg_gen (hit.c:347-401: the hits'
+ *                                       anchors split by segment, mm_gen_regs per segment with the fragment's hash and the segment's
+ *                                       length, seg_split = 1, seg_id = the segment); per segment mm_set_parent and, unless
+ *                                       opt->flag & MM_F_CIGAR, mm_set_mapq with the fragment's rep_len (map.c:882-886).
+ *                                       mm_est_err is not run for these reads: mm_seg_gen rebuilds the records, so div is -1.0f in
+ *                                       every split hit.  mm_pair (MM_F_CIGAR only) and mm_set_pe_thru are not here.
+ *   n_segs_per_read[n_reads] may be NULL (the segments the batch was chained with); if given it must equal them.  seg_len[n_seqs]
+ *   may be NULL: the lengths the last chaindp_sketch saw.  Each read's seg_len must add up to the qlen chaindp_gen_regs was given.
+ *   rep_len[n_reads], mini_pos_off / mini_pos, ref_len / n_ref as in chaindp_chain_post (mini_pos is needed only when !opt->is_sr and the
+ *   batch holds a one-segment read; mm_est_err then runs over the batch's packed hits and only those reads keep its div).
+ *   seg_regs_off[n_seqs + 1] receives the CSR offsets of every segment's final hits, regs the records (room for regs_cap of them:
+ *   CHAINDP_ERR_CAPACITY, with seg_regs_off filled in, if there are more).
+ *   seg_a_off[n_seqs + 1] / seg_a (both optional; seg_a needs b_off[n_reads] entries): each segment's anchors (mm_seg_t::a, y
+ *   relative to the segment; for a one-segment read the anchors as chain_post left them), which `as` of the returned hits indexes.
+ *   With MM_F_CIGAR the call stops after the per-segment mm_set_parent and these are what the host's align_regs needs.
+ * The results go to buffers of the call's own; what chaindp_backtrack and chaindp_gen_regs left stays as it was.  Refusals as
+ * chaindp_chain_post's (but for n_segs > 1), plus segments that do not add up. */
+int chaindp_frag_post(chaindp_ctx_t *ctx, const chaindp_post_opt_t *opt, int64_t n_seqs, const int32_t *n_segs_per_read, const int32_t *seg_len,
+                      const int32_t *rep_len, const int32_t *ref_len, int32_t n_ref, const int64_t *mini_pos_off, const uint64_t *mini_pos,
+                      int64_t *seg_regs_off, chaindp_reg_t *regs, int64_t regs_cap, int64_t *seg_a_off, chaindp_anchor_t *seg_a);
+/* chaindp_map_batch (with the reads' segment counts) followed by chaindp_frag_post in one resident call: minimizers in, per-segment
+ * final hits out.  Arguments as chaindp_map_reads' plus n_seqs, n_segs_per_read (required) and seg_len; mini == NULL && mini_off ==
+ * NULL takes the minimizers of the last chaindp_sketch (qlen and seg_len may then be NULL too).
+ * One par per call, as everywhere in this ABI: the reference derives the `sr` gaps from qlen_sum (map.c:358-366), so a caller with
+ * reads of mixed lengths groups them by gap into separate calls, as fpga_shim.cpp does for its packets.  Per-read gaps are not
+ * supported. */
+int chaindp_map_frags(chaindp_ctx_t *ctx, const chaindp_index_t *idx, int flag, int max_occ, const chaindp_params_t *par, int min_cnt,
+                      const chaindp_post_opt_t *opt, int64_t n_reads, const int64_t *mini_off, const chaindp_anchor_t *mini, const uint32_t *bid,
+                      const int32_t *qlen, const uint32_t *hash, int64_t n_seqs, const int32_t *n_segs_per_read, const int32_t *seg_len,
+                      const int32_t *ref_len, int32_t n_ref, int64_t *seg_regs_off, chaindp_reg_t *regs, int64_t regs_cap, int32_t *rep_len,
+                      int64_t *n_anchors);
+/* chaindp_sketch (with n_segs_per_read) followed by chaindp_map_frags: bases in, per-segment final hits out.  pe_ori = -1 leaves the
+ * reads alone; otherwise (0..3) a read of exactly two segments is treated as worker_for treats it around mm_map_frag (map.c:608-631):
+ * segment 0 is reverse-complemented before the sketch if pe_ori >> 1 & 1, segment 1 if pe_ori & 1 (on the device, on the call's copy
+ * of the bases: A <-> T, C <-> G, U -> A, everything else stays ambiguous), and afterwards those segments' hits get
+ * qs, qe = qlen - qe, qlen - qs and rev flipped.  Reads of one or of more than two segments are untouched by any pe_ori.  Bit-identical
+ * to the separate calls for pe_ori = -1. */
+int chaindp_map_frag_seqs(chaindp_ctx_t *ctx, const chaindp_index_t *idx, int w, int k, int is_hpc, int flag, int max_occ,
+                          const chaindp_params_t *par, int min_cnt, const chaindp_post_opt_t *opt, int pe_ori, int64_t n_reads, int64_t n_seqs,
+                          const int32_t *n_segs_per_read, const int64_t *seq_off, const char *seq, const uint32_t *bid, const uint32_t *hash,
+                          const int32_t *ref_len, int32_t n_ref, int64_t *seg_regs_off, chaindp_reg_t *regs, int64_t regs_cap, int32_t *rep_len,
+                          int64_t *n_anchors);
 /* With profiling on (chaindp_set_profiling): device time of the sketch kernels and scans accumulated over `calls` chaindp_sketch calls. */
 int chaindp_get_sketch_ms(chaindp_ctx_t *ctx, double *ms, int64_t *calls, int reset);
 

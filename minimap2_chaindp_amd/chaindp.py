@@ -31,6 +31,7 @@ ABI_SYMBOLS = (
     "chaindp_pipe_last_error", "chaindp_map_batch",
     "chaindp_chain_post", "chaindp_map_reads", "chaindp_post_logf_selftest", "chaindp_post_logf_patches",
     "chaindp_sketch", "chaindp_download_minimizers", "chaindp_map_seqs", "chaindp_get_sketch_ms",
+    "chaindp_frag_post", "chaindp_map_frags", "chaindp_map_frag_seqs",
 )
 
 # chaindp_reg_t == mm_reg1_t (minimap.h:100-115), 80 bytes; `bits` is the bit-field word (rev = bit 10)
@@ -102,6 +103,10 @@ def lib():
         L.chaindp_download_minimizers.argtypes = [vp, vp]
         L.chaindp_map_seqs.argtypes = [vp, vp, i32, i32, i32, i32, i32, P, i32, PO, i64, vp, vp, vp, vp, vp, i32, vp, vp, i64, vp, vp]
         L.chaindp_get_sketch_ms.argtypes = [vp, vp, vp, i32]
+        L.chaindp_frag_post.argtypes = [vp, PO, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp]
+        L.chaindp_map_frags.argtypes = [vp, vp, i32, i32, P, i32, PO, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, i32, vp, vp, i64, vp, vp]
+        L.chaindp_map_frag_seqs.argtypes = [vp, vp, i32, i32, i32, i32, i32, P, i32, PO, i32, i64, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, i64, vp, vp]
+        L.chaindp_debug_set_frag_lds_cap.argtypes = [vp, i32]
         L.chaindp_post_logf_selftest.restype = i64
         L.chaindp_post_logf_selftest.argtypes = [vp, i32]
         L.chaindp_post_logf_patches.restype = i64
@@ -409,6 +414,96 @@ class Device:
         else:
             self._check(rc)
         return roff, regs[:int(roff[-1])], rep[:n_reads], int(na.value)
+
+    # -- reads of several segments (paired reads): chain_post with mm_select_sub_multi, mm_seg_gen, per-segment mm_set_parent / mm_set_mapq
+    def frag_post(self, opt, ref_len, n_segs, seg_len=None, rep_len=None, mini_pos_off=None, mini_pos=None, regs_cap=None, want_anchors=False):
+        """The final hits of every segment (chaindp_frag_post) from the hits gen_regs() left on the device: (seg_regs_off int64[n_seqs+1],
+        regs REG_DTYPE[...]) and, with want_anchors, (seg_a_off int64[n_seqs+1], seg_a uint64[...,2]): every segment's anchors.  n_segs
+        int32[n_reads]: the segments of every read (1..255), as the batch was chained; seg_len int32[n_seqs] (None: the lengths the last
+        sketch() saw); rep_len / mini_pos None: the ones on the device.  regs_cap None: retried with the exact count if a guess is short."""
+        ns = np.ascontiguousarray(n_segs, np.int32)
+        n_seqs = int(ns.sum())
+        ref_len = np.ascontiguousarray(ref_len, np.int32)
+        sl = None if seg_len is None else np.ascontiguousarray(seg_len, np.int32)
+        rl = None if rep_len is None else np.ascontiguousarray(rep_len, np.int32)
+        mpo = None if mini_pos_off is None else np.ascontiguousarray(mini_pos_off, np.int64)
+        mp = None if mini_pos is None else np.ascontiguousarray(mini_pos, np.uint64)
+        cap = int(regs_cap) if regs_cap is not None else max(self._total // 4, 1024)
+        aoff = np.zeros(n_seqs + 1, np.int64) if want_anchors else None
+        a = np.zeros((max(self._total, 1), 2), np.uint64) if want_anchors else None
+        while True:
+            soff = np.zeros(n_seqs + 1, np.int64)
+            regs = np.zeros(max(cap, 1), REG_DTYPE)
+            rc = self._lib.chaindp_frag_post(self._ctx, C.byref(opt), n_seqs, _ptr(ns), _ptr(sl), _ptr(rl), _ptr(ref_len) if len(ref_len) else None,
+                                             len(ref_len), _ptr(mpo), None if mp is None or not len(mp) else _ptr(mp), _ptr(soff), _ptr(regs), cap,
+                                             _ptr(aoff), _ptr(a))
+            if rc == -2 and regs_cap is None and int(soff[-1]) > cap:          # more hits than guessed: again with room for them
+                cap = int(soff[-1])
+                continue
+            self._check(rc)
+            break
+        regs = regs[:int(soff[-1])]
+        return (soff, regs, aoff, a[:int(aoff[-1])]) if want_anchors else (soff, regs)
+
+    def map_frags(self, index, flag, max_occ, par, min_cnt, opt, mini_off, mini, bid, qlen, hash_, n_segs, seg_len, ref_len, regs_cap=None):
+        """Minimizers in, per-segment final hits out (chaindp_map_frags): (seg_regs_off int64[n_seqs+1], regs REG_DTYPE[...], rep_len
+        int32[n_reads], n_anchors).  mini_off = mini = None: the minimizers the last sketch() left on the device (qlen = seg_len = None
+        then: the lengths it saw).  One `par` per call: group reads by their gap parameters."""
+        ns = np.ascontiguousarray(n_segs, np.int32)
+        n_seqs = int(ns.sum())
+        if mini_off is None and mini is None:
+            n_reads, n_mini = len(bid), self._sk_n_mini
+        else:
+            mini_off = np.ascontiguousarray(mini_off, np.int64)
+            n_reads = len(mini_off) - 1
+            mini = np.ascontiguousarray(mini, np.uint64).reshape(-1, 2)
+            n_mini = len(mini)
+        bid = np.ascontiguousarray(bid, np.uint32); hash_ = np.ascontiguousarray(hash_, np.uint32)
+        qlen = None if qlen is None else np.ascontiguousarray(qlen, np.int32)
+        sl = None if seg_len is None else np.ascontiguousarray(seg_len, np.int32)
+        ref_len = np.ascontiguousarray(ref_len, np.int32)
+        cap = int(regs_cap) if regs_cap is not None else max(n_mini // 2, 1024)
+        soff = np.zeros(n_seqs + 1, np.int64); rep = np.zeros(max(n_reads, 1), np.int32)
+        regs = np.zeros(max(cap, 1), REG_DTYPE)
+        na = C.c_int64(0)
+        rc = self._lib.chaindp_map_frags(self._ctx, index, int(flag), int(max_occ), C.byref(par), int(min_cnt), C.byref(opt), n_reads, _ptr(mini_off),
+                                         _ptr(mini), _ptr(bid), _ptr(qlen), _ptr(hash_), n_seqs, _ptr(ns), _ptr(sl), _ptr(ref_len) if len(ref_len) else None,
+                                         len(ref_len), _ptr(soff), _ptr(regs), cap, _ptr(rep), C.byref(na))
+        self._n_reads, self._total = n_reads, int(na.value)
+        if rc == -2 and regs_cap is None and int(soff[-1]) > cap:              # more hits than guessed: run the post steps again with room for them
+            soff, regs = self.frag_post(opt, ref_len, ns, seg_len=sl, regs_cap=int(soff[-1]))
+        else:
+            self._check(rc)
+        return soff, regs[:int(soff[-1])], rep[:n_reads], int(na.value)
+
+    def map_frag_seqs(self, index, w, k, is_hpc, flag, max_occ, par, min_cnt, opt, seq, seq_off, n_segs, bid, hash_, ref_len, pe_ori=-1, regs_cap=None):
+        """Bases in, per-segment final hits out (chaindp_map_frag_seqs = sketch(n_segs) + map_frags()): (seg_regs_off, regs, rep_len,
+        n_anchors).  pe_ori 0..3: a pair's segments are reverse-complemented on the device before the sketch and their hits flipped back
+        afterwards, as the reference's worker_for does (map.c:608-631); -1 leaves the reads alone."""
+        seq, seq_off = self._seqs(seq, seq_off)
+        ns = np.ascontiguousarray(n_segs, np.int32)
+        n_reads, n_seqs = len(ns), len(seq_off) - 1
+        bid = np.ascontiguousarray(bid, np.uint32); hash_ = np.ascontiguousarray(hash_, np.uint32); ref_len = np.ascontiguousarray(ref_len, np.int32)
+        cap = int(regs_cap) if regs_cap is not None else max(len(seq) // 16, 1024)
+        while True:
+            soff = np.zeros(n_seqs + 1, np.int64); rep = np.zeros(max(n_reads, 1), np.int32)
+            regs = np.zeros(max(cap, 1), REG_DTYPE)
+            na = C.c_int64(0)
+            rc = self._lib.chaindp_map_frag_seqs(self._ctx, index, int(w), int(k), int(bool(is_hpc)), int(flag), int(max_occ), C.byref(par), int(min_cnt),
+                                                 C.byref(opt), int(pe_ori), n_reads, n_seqs, _ptr(ns), _ptr(seq_off), _ptr(seq) if len(seq) else None, _ptr(bid),
+                                                 _ptr(hash_), _ptr(ref_len) if len(ref_len) else None, len(ref_len), _ptr(soff), _ptr(regs), cap, _ptr(rep),
+                                                 C.byref(na))
+            self._n_reads, self._total = n_reads, int(na.value)
+            if rc == -2 and regs_cap is None and int(soff[-1]) > cap:          # more hits than guessed: the whole call again (the flip is part of it)
+                cap = int(soff[-1])
+                continue
+            self._check(rc)
+            break
+        return soff, regs[:int(soff[-1])], rep[:n_reads], int(na.value)
+
+    def set_frag_lds_cap(self, cap=64):
+        """Test hook: fragments (and segments) with more than `cap` hits (0..64) keep their work arrays in global scratch, not LDS."""
+        self._check(self._lib.chaindp_debug_set_frag_lds_cap(self._ctx, int(cap)))
 
     def sketch_ms(self, reset=False):
         """(device ms, calls) of the sketch kernels accumulated while profiling is on."""

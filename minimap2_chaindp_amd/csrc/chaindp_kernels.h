@@ -182,6 +182,25 @@ hipError_t launch_post_mapq(hipStream_t st, int64_t n_reads, const unsigned long
                             const uint32_t *d_pk, const float *d_pv, int n_patch, void *d_out, int32_t *d_err);
 hipError_t launch_post_logf_probe(hipStream_t st, int kmax, const uint32_t *d_pk, const float *d_pv, int n_patch, float *d_out, int32_t *d_term);
 
+// reads of several segments: chain_post with mm_select_sub_multi, mm_seg_gen, per-segment mm_set_parent (pe.c:6-43, hit.c:347-401,
+// map.c:878-886): chaindp_frag.hip.  d_read_seq0[n_reads + 1]: first sequence of every read; the per-sequence arrays have n_seqs entries,
+// the count / offset arrays n_seqs + 1.  lds_cap (tests): hits per fragment or segment kept in LDS, at most FRAG_LDS_CAP.
+#define FRAG_LDS_CAP 64                  // 20 ints per hit: 5 KB per one-wave workgroup; more hits go through global scratch
+hipError_t launch_frag_read(hipStream_t st, int64_t n_reads, const int64_t *d_chains_off, const int64_t *d_b_off, const void *d_b, const void *d_regs,
+                            const int32_t *d_qlen, const int32_t *d_read_seq0, const int32_t *d_seq_len, const PostOpt &o, int max_gap_ref, int lds_cap,
+                            int32_t *d_scratch, void *d_stage, void *d_sq, unsigned long long *d_n_out, unsigned long long *d_cnt_g,
+                            unsigned long long *d_cnt_o, unsigned long long *d_cnt_a);
+hipError_t launch_frag_split(hipStream_t st, int64_t n_reads, const unsigned long long *d_post_off, const void *d_post_out, const int64_t *d_b_off,
+                             const void *d_sq, const int32_t *d_read_seq0, const int32_t *d_seq_len, const uint32_t *d_hash, const int32_t *d_rep_len,
+                             const unsigned long long *d_g_off, const unsigned long long *d_o_off, const unsigned long long *d_a_off,
+                             unsigned long long *d_seg_u, void *d_seg_a, void *d_out, uint32_t *d_seq_hash, int32_t *d_seq_rep, int32_t *d_seq_read);
+hipError_t launch_frag_seg(hipStream_t st, int64_t n_seqs, const int32_t *d_read_seq0, const int32_t *d_seq_read, const unsigned long long *d_g_off,
+                           const unsigned long long *d_o_off, const void *d_seg_stage, float mask_level, int lds_cap, int32_t *d_scratch, void *d_out);
+// worker_for's reverse complement of a pair's segments before the sketch and the flip of their hits afterwards (map.c:608-631)
+hipError_t launch_frag_revcomp(hipStream_t st, int64_t n_reads, const int32_t *d_read_seq0, const int64_t *d_seq_off, uint8_t *d_seq, int pe_ori);
+hipError_t launch_frag_flip(hipStream_t st, int64_t n_seqs, const int32_t *d_read_seq0, const int32_t *d_seq_read, const int32_t *d_seq_len,
+                            const unsigned long long *d_o_off, int pe_ori, void *d_out);
+
 // seed collection on the GPU (reference map.c:112-236 over the FPGA index image, index.c:603-720): chaindp_seed.hip
 // The four blobs of the image, as index.c:603-720 writes them:
 //   B: per hash bucket 16 bytes: w0 = (p_off & 0xff) << 56 | n_buckets << 24;  w1 = h_off << 28 | p_off >> 8

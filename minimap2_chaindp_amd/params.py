@@ -66,6 +66,8 @@ POST_PRESETS = {
     "map-pb": dict(min_diff=2 * 19),
     "ava-ont": dict(min_diff=2 * 15, flag=MM_F_ALL_CHAINS | MM_F_NO_DIAG | MM_F_NO_DUAL | MM_F_NO_LJOIN, min_chain_score=100, pri_ratio=0.0),
     "ava-pb": dict(min_diff=2 * 19, flag=MM_F_ALL_CHAINS | MM_F_NO_DIAG | MM_F_NO_DUAL | MM_F_NO_LJOIN, min_chain_score=100, pri_ratio=0.0),
+    # options.c:115-131: paired short reads (k = 21, a = 2, b = 8); chaindp_frag_post / map_frags / map_frag_seqs
+    "sr": dict(min_diff=2 * 21, flag=MM_F_SR, pri_ratio=0.5, best_n=20, min_cnt=2, min_chain_score=25, match_sc=2, sub_diff=2 * 2 + 8, is_sr=1),
 }
 
 
