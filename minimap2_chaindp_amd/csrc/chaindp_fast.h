@@ -199,11 +199,15 @@ __device__ __forceinline__ void fast_flush_tile(const UnitCtx &c, int tile0, int
 		val = vext > val ? vext : val;
 		ptr = -1;
 	}
+	// Pointer doubling: lanes whose pointer has left the tile (or that hold no anchor: -1) read themselves, pv = val and pp = ptr.
+	// A round that would raise no lane's value leaves every value final -- val[ptr] <= val wherever ptr is inside the tile, so
+	// v = val lane by lane in tile order (p[i] < i) --, and that is the first or second round in most tiles, not the sixth.
 	for (int r = 0; r < 6; ++r) {
 		const int src = (ptr >= tile0 ? ptr - tile0 : lane) << 2;
 		const int pv = __builtin_amdgcn_ds_bpermute(src, val);
-		const int pp = __builtin_amdgcn_ds_bpermute(src, ptr);
-		if (ptr >= tile0) { val = pv > val ? pv : val; ptr = pp; }
+		if (__builtin_amdgcn_ballot_w64(pv > val) == 0) break;
+		ptr = __builtin_amdgcn_ds_bpermute(src, ptr);
+		val = pv > val ? pv : val;
 	}
 	wave_mem_fence();
 	if (lane < cnt) lds_store_b32(L::V_OFF + (waddr >> 2), val);

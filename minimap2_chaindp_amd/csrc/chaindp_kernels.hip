@@ -310,7 +310,7 @@ __device__ __forceinline__ void run_unit(const UnitCtx &c, int64_t room)
 //   * prefix-max lanes without a source read 0 instead of INT_MIN: the running max is >= q_span >= 0, so a
 //     floor of 0 changes nothing and saves the copy in front of the DPP chain;
 //   * v[] (chain.c:284) is not part of the recurrence at all: v[i] = max(f[i], v[p[i]]) is computed per 64-anchor
-//     tile at flush time by pointer doubling over the tile (6 rounds of ds_bpermute), not per anchor.
+//     tile at flush time by pointer doubling over the tile (up to 6 rounds of ds_bpermute: fast_flush_tile), not per anchor.
 
 // One chunk of 64 ring predecessors of anchor i (lane k <-> j = jtop - k, S = 16 * jtop): scores, marks, and the
 // lane masks A ("new running max", chain.c:274) and B ("marked and not better", chain.c:277).  Straight-line code.

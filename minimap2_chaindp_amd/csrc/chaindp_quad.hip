@@ -314,12 +314,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 				const int vext = __builtin_amdgcn_ds_bpermute((ext ? ptr - (tile_prev - QD_TILE) : lane) << 2, vprev);
 				if (ext) { val = max(val, vext & 0x7fffffff); ptr = -1; }
 				const bool ext_self = ext && vext < 0;
-				for (int r = 0; r < 6; ++r) {                                // v[i] = max(f[i], v[p[i]]) (chain.c:284) by pointer doubling over the tile
-					if (__builtin_amdgcn_ballot_w64(ptr >= tile_prev) == 0) break;
-					const int src = (ptr >= tile_prev ? ptr - tile_prev : lane) << 2;
-					const int pv = __builtin_amdgcn_ds_bpermute(src, val);
-					const int pp = __builtin_amdgcn_ds_bpermute(src, ptr);
-					if (ptr >= tile_prev) { val = max(val, pv); ptr = pp; }
+				// v[i] = max(f[i], v[p[i]]) (chain.c:284) by pointer doubling over the tile; a round that would raise no lane's value
+				// leaves every value final (chaindp_twin.hip)
+				if (__builtin_amdgcn_ballot_w64(ptr >= tile_prev) != 0) {
+					int r = 0;
+					do {
+						const int src = (ptr >= tile_prev ? ptr - tile_prev : lane) << 2;
+						const int pv = __builtin_amdgcn_ds_bpermute(src, val);
+						if (__builtin_amdgcn_ballot_w64(pv > val) == 0) break;
+						ptr = __builtin_amdgcn_ds_bpermute(src, ptr);
+						val = max(val, pv);
+					} while (++r < 6 && __builtin_amdgcn_ballot_w64(ptr >= tile_prev) != 0);
 				}
 				const bool self = val >= g.par.min_sc || pi >= 0;            // emitted at its own step (chain.c:304)
 				const int srcp = (pi >= tile_prev ? pi - tile_prev : lane) << 2;

@@ -379,7 +379,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 	int32_t pfu0 = -1, pfu1 = -1;                                  // (PF) ... or, when the unit ends with the current tile, the first tile of the half's
 	                                                               // next unit: its first anchor's global index (wave-uniform), -1 = no such tile
 
-	TW_STAMP(unsigned long long st_t0 = 0; unsigned int st_service = 0, st_n_service = 0, st_n_fast = 0, st_flush = 0, st_unit = 0, st_n_unit = 0, st_head = 0, st_take = 0, st_tail = 0;)   // (32-bit sums: a wave's ticks fit, and the build has no registers to spare)
+	TW_STAMP(unsigned long long st_t0 = 0; unsigned int st_service = 0, st_n_service = 0, st_n_fast = 0, st_flush = 0, st_unit = 0, st_n_unit = 0, st_head = 0, st_take = 0, st_tail = 0, st_rounds = 0, st_n_flush = 0;)   // (32-bit sums: a wave's ticks fit, and the build has no registers to spare)
 
 	// One service round for the halves in `svc`, whose tile is exhausted (or which have no unit yet).  One half at a time, by ALL 64
 	// lanes of the wave (a tile is 64 anchors, one per lane): everything that is per half (the cold state, the unit being picked,
@@ -535,13 +535,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 					ptr = -1;
 				}
 				const bool ext_self = ext && vext < 0;                       // (bit 31 of a V entry: the anchor was emitted at its own step)
-				for (int r = 0; r < 6; ++r) {                                // v[i] = max(f[i], v[p[i]]) (chain.c:284) by pointer doubling over the tile
-					if (__builtin_amdgcn_ballot_w64(ptr >= tile_prev) == 0) break;
-					const int src = (ptr >= tile_prev ? ptr - tile_prev : lane) << 2;
-					const int pv = __builtin_amdgcn_ds_bpermute(src, val);
-					const int pp = __builtin_amdgcn_ds_bpermute(src, ptr);
-					if (ptr >= tile_prev) { val = max(val, pv); ptr = pp; }
+				// v[i] = max(f[i], v[p[i]]) (chain.c:284) by pointer doubling over the tile: after r rounds val is the maximum of f over the
+				// lane and its first 2^r - 1 in-tile ancestors (and the final v of an ancestor in an earlier tile), ptr the ancestor after those.
+				// Lanes whose pointer has left the tile read themselves, so pv = val and pp = ptr there.  Two ways out.  No pointer is
+				// inside the tile any more: at most six rounds.  And a round that would raise no lane's value: then val[ptr] <= val
+				// wherever ptr is inside the tile, and v = val follows lane by lane in tile order (p[i] < i: v[ptr] = val[ptr] by
+				// induction, so v = max(val, v[ptr]) = val).  Chains run up through a tile and f mostly grows along them, so this is
+				// the first round in nearly every tile (profiles/r08_*): one ds_bpermute where there were twelve.
+				if (__builtin_amdgcn_ballot_w64(ptr >= tile_prev) != 0) {
+					int r = 0;
+					do {
+						TW_STAMP_A(if (g.stamp) ++st_rounds;)
+						const int src = (ptr >= tile_prev ? ptr - tile_prev : lane) << 2;
+						const int pv = __builtin_amdgcn_ds_bpermute(src, val);
+						if (__builtin_amdgcn_ballot_w64(pv > val) == 0) break;
+						ptr = __builtin_amdgcn_ds_bpermute(src, ptr);
+						val = max(val, pv);
+					} while (++r < 6 && __builtin_amdgcn_ballot_w64(ptr >= tile_prev) != 0);
 				}
+				TW_STAMP_A(if (g.stamp) ++st_n_flush;)
 				const bool self = val >= min_sc || pi >= 0;            // emitted at its own step (chain.c:304)
 				// is the predecessor emitted at its own step?  in-tile predecessors: ask their lane
 				const int srcp = (pi >= tile_prev ? pi - tile_prev : lane) << 2;
@@ -974,7 +986,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 	}
 	TW_STAMP(if (g.stamp && lane == 0) {
 		unsigned long long *o = g.stamp + 12 * (size_t)blockIdx.x;
-		o[0] = TW_NOW() - st_t0; o[1] = st_service; o[2] = st_flush; o[3] = st_unit; o[4] = st_n_service; o[5] = st_n_fast; o[6] = st_n_unit; o[7] = 1; o[8] = st_head; o[9] = st_take; o[10] = st_tail;
+		o[0] = TW_NOW() - st_t0; o[1] = st_service; o[2] = st_flush; o[3] = st_unit; o[4] = st_n_service; o[5] = st_n_fast; o[6] = st_n_unit; o[7] = 1; o[8] = st_head; o[9] = st_take; o[10] = st_tail; o[11] = (unsigned long long)st_n_flush << 32 | st_rounds;
 	})
 #undef TW_COLD
 }
@@ -1027,12 +1039,13 @@ static hipError_t launch_twin_layout(hipStream_t st, TwinArgs g, int64_t max_uni
 	if (g.stamp) {
 		std::vector<unsigned long long> hb((size_t)blocks * 12);
 		if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(hb.data(), d_stamp, hb.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-			double tot = 0, svc = 0, flush = 0, unit = 0, nsvc = 0, nfast = 0, nunit = 0, nb = 0, head = 0, take = 0, tail = 0;
+			double tot = 0, svc = 0, flush = 0, unit = 0, nsvc = 0, nfast = 0, nunit = 0, nb = 0, head = 0, take = 0, tail = 0, rounds = 0, nflush = 0;
 			for (int64_t b = 0; b < blocks; ++b) if (hb[(size_t)b * 12 + 7]) {
 				const unsigned long long *o = &hb[(size_t)b * 12];
-				tot += o[0]; svc += o[1]; flush += o[2]; unit += o[3]; nsvc += o[4]; nfast += o[5]; nunit += o[6]; head += o[8]; take += o[9]; tail += o[10]; ++nb;
+				tot += o[0]; svc += o[1]; flush += o[2]; unit += o[3]; nsvc += o[4]; nfast += o[5]; nunit += o[6]; head += o[8]; take += o[9]; tail += o[10]; rounds += (double)(o[11] & 0xffffffffull); nflush += (double)(o[11] >> 32); ++nb;
 			}
 			if (nb > 0) fprintf(stderr, "[twin stamp raw] sums over waves: head %.0f take %.0f tail %.0f unit %.0f n_unit %.0f (build 3: ticks until the record / the first tile / the rest of a unit switch; switches; first tiles requested ahead)\n", head, take, tail, unit, nunit);
+			if (nflush > 0) fprintf(stderr, "[twin stamp flush] %.0f tiles flushed, %.0f rounds of the v[] loop: %.3f a tile (build 1)\n", nflush, rounds, rounds / nflush);
 			if (nb > 0) fprintf(stderr, "[twin stamp] %.0f waves, %.0f ticks each: service %.1f%% (%.0f calls, %.0f ticks each: cold state and decisions %.0f, next tile %.0f, flush %.0f, "
 			                "unit switch %.0f (%.0f switches, %.0f ticks each), first anchor and cold state back %.0f), passes %.0f (%.0f ticks each, everything else included)\n",
 			        nb, tot / nb, 100.0 * svc / tot, nsvc, svc / (nsvc > 0 ? nsvc : 1), head / (nsvc > 0 ? nsvc : 1), take / (nsvc > 0 ? nsvc : 1), flush / (nsvc > 0 ? nsvc : 1),
