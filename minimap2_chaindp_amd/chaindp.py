@@ -548,6 +548,12 @@ class Device:
         self._lib.chaindp_debug_leftover.argtypes = [C.c_void_p]
         return int(self._lib.chaindp_debug_leftover(self._ctx))
 
+    def device_bytes(self):
+        """Bytes of device memory the context owns at this moment (test hook)."""
+        self._lib.chaindp_debug_device_bytes.restype = C.c_int64
+        self._lib.chaindp_debug_device_bytes.argtypes = [C.c_void_p]
+        return int(self._lib.chaindp_debug_device_bytes(self._ctx))
+
     def deep_units(self):
         """Units the one-per-wave kernel handed over to k_chain_dense in the last run (test / tuning hook)."""
         self._lib.chaindp_debug_deep_units.restype = C.c_int64

@@ -13,6 +13,7 @@
 #include <vector>
 #include "../../include/chaindp.h"
 #include "chaindp_kernels.h"
+#include "chaindp_devmem.h"
 
 using chaindp::Params;
 using chaindp::Unit;
@@ -23,12 +24,14 @@ struct EventSet { hipEvent_t e[3]; int n; int slot0; };  // e[0..n): consecutive
 
 struct chaindp_ctx {
 	int device = -1;
+	// every device buffer below is an entry of this pool: allocated, grown and freed through it and nowhere else
+	chaindp::DevPool pool{[](void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }, [](void *p) { return (int)hipFree(p); }};
 	hipStream_t stream = nullptr;
 	int64_t cap_anchors = 0, cap_reads = 0;
 	int ring = 128;
 	// resident batch
 	int64_t n_reads = 0, total = 0, n_seeds = 0;
-	bool has_n_segs = false, ran = false, compact_ready = false;
+	bool has_n_segs = false, ran = false;
 	bool singles_pending = false;    // the last run left f, p, v, flags[] of its singletons to k_fill_singles (chaindp_download runs it)
 	chaindp_params_t ran_par{};      // the parameters of that run
 	int64_t *d_off = nullptr;
@@ -58,11 +61,11 @@ struct chaindp_ctx {
 	chaindp::PrepassScratch pre = {nullptr, nullptr, nullptr, nullptr, nullptr};
 	chaindp::CompactScratch cmp = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 	chaindp::BottomScratch bot = {};
-	bool bot_ready = false, seed_ready = false;   // first-use allocations complete
-	std::vector<void*> bot_allocs;
+	// first-use groups of buffers: each flag is set once, after its group's allocations have all succeeded, and never reset
+	bool compact_ready = false, bot_ready = false, seed_ready = false, regs_ready = false, post_ready = false, logf_ready = false;
 	uint16_t *d_lut = nullptr;
 	void **d_ptrs = nullptr;         // per-read host pointers for the gather / scatter kernels
-	size_t ptr_cap = 0;
+	size_t ptr_bytes = 0;
 	size_t lut_bytes = 0;
 	bool use_lut = true;
 	// compaction (allocated on first use)
@@ -80,7 +83,7 @@ struct chaindp_ctx {
 	int64_t seed_cap_mini = 0, n_mini_pos = 0;
 	int seed_max_n = -1, seed_max_n2 = -1; // largest reads the two configurations of the LDS sort take on this device
 	int seed_lab_cap = 0;                  // digits k_seed_sort_huge keeps in LDS
-	// chains to hits (allocated on first use, grown with the batch; freed with bot_allocs)
+	// chains to hits (allocated on first use, grown with the batch)
 	void *d_regs = nullptr, *d_reg_counts = nullptr, *d_ref_len = nullptr, *d_mp_up = nullptr;
 	size_t regs_cap = 0, reg_counts_cap = 0, ref_len_cap = 0, mp_up_cap = 0;
 	uint32_t *d_rhash = nullptr;
@@ -90,22 +93,21 @@ struct chaindp_ctx {
 	int64_t bot_n_reads = -1, bot_n_chains = 0, bot_n_b = 0;   // what the last chaindp_backtrack left resident (-1: nothing of this batch)
 	bool mp_resident = false;                                  // this batch's mini_pos are on the device (it came from chaindp_collect_seeds)
 	bool regs_resident = false;      // d_regs / d_rqlen hold what chaindp_gen_regs made of the resident chains (chaindp_est_err's upload clears it)
-	// chain_post + mm_set_mapq (allocated on first use, grown with the batch; freed with bot_allocs)
+	// chain_post + mm_set_mapq (allocated on first use, grown with the batch)
 	void *d_post_stage = nullptr, *d_post_out = nullptr, *d_post_sq = nullptr, *d_post_scratch = nullptr;
 	size_t post_stage_cap = 0, post_out_cap = 0, post_sq_cap = 0, post_scratch_cap = 0;
 	unsigned long long *d_post_off = nullptr, *d_post_tile = nullptr;
 	int32_t *d_post_qlen = nullptr, *d_post_rep = nullptr, *d_post_err = nullptr;
 	uint32_t *d_logf_k = nullptr;
 	float *d_logf_v = nullptr;
-	int n_logf = -1;
-	// reads of several segments: chaindp_frag_post (allocated on first use, grown with the batch; freed with bot_allocs)
+	int n_logf = 0;
+	// reads of several segments: chaindp_frag_post (allocated on first use, grown with the batch)
 	void *d_frag_seq = nullptr, *d_frag_cnt = nullptr, *d_frag_u = nullptr, *d_frag_a = nullptr, *d_frag_stage = nullptr, *d_frag_z = nullptr;
 	void *d_frag_stacks = nullptr, *d_frag_out = nullptr;
 	size_t frag_seq_cap = 0, frag_cnt_cap = 0, frag_u_cap = 0, frag_a_cap = 0, frag_stage_cap = 0, frag_z_cap = 0, frag_stacks_cap = 0, frag_out_cap = 0;
 	int frag_lds_cap = FRAG_LDS_CAP;           // chaindp_debug_set_frag_lds_cap (tests): fewer hits per fragment stay in LDS
 	// sketch (allocated on first use, grown with the batch)
 	chaindp::SketchArgs sk = {};
-	std::vector<void*> sk_allocs;
 	int64_t sk_cap_bases = -1, sk_cap_chunks = -1, sk_cap_seqs = -1;
 	int64_t sk_max_bases = 0x7fffff00;         // CHAINDP_SKETCH_MAX_BASES (test switch) lowers it; positions and ranks are 32-bit
 	unsigned long long *d_sk_totals = nullptr;
@@ -126,6 +128,7 @@ struct chaindp_ctx {
 	std::string err;
 };
 
+// (ctx: a context or a pipe)
 #define HIP_TRY(ctx, call)                                                                         \
 	do {                                                                                           \
 		hipError_t e_ = (call);                                                                    \
@@ -134,6 +137,58 @@ struct chaindp_ctx {
 			return CHAINDP_ERR_HIP;                                                                \
 		}                                                                                          \
 	} while (0)
+
+using chaindp::dev_buf;
+
+// A first-use group of buffers, all or nothing: an out-of-memory half way leaves the context as it was (what this attempt allocated
+// is freed again and the next call tries anew) instead of half-initialised with kernels launched on null scratch pointers.
+static int first_use(chaindp_ctx *ctx, bool &ready, const char *what, std::initializer_list<chaindp::DevBuf> bufs)
+{
+	if (ready) return CHAINDP_OK;
+	const hipError_t e = (hipError_t)ctx->pool.alloc_group(bufs);
+	if (e != hipSuccess) { ctx->err = std::string(what) + " buffers: " + hipGetErrorString(e); return CHAINDP_ERR_HIP; }
+	ready = true;
+	return CHAINDP_OK;
+}
+
+// grow-only device buffer with a quarter of slack; a failed growth leaves the old buffer and its capacity
+static hipError_t dev_grow(chaindp_ctx *ctx, void *&p, size_t &cap, size_t need)
+{
+	return (hipError_t)ctx->pool.reserve(&p, cap, need, need + need / 4, false);
+}
+
+// A new batch is resident (or, with 0 reads, none): what the calls on the one before left is no longer of this batch.
+static void begin_batch(chaindp_ctx *ctx, int64_t n_reads, int64_t total, bool mp_resident = false)
+{
+	ctx->n_reads = n_reads; ctx->total = total; ctx->ran = false; ctx->bot_n_reads = -1; ctx->mp_resident = mp_resident;
+}
+
+// the batch's per-read segment counts, if it has any, on the stream that carries its upload
+static hipError_t stage_n_segs(chaindp_ctx *ctx, const int32_t *n_segs_per_read, int64_t n_reads, hipStream_t st)
+{
+	ctx->has_n_segs = n_segs_per_read != nullptr;
+	if (!n_segs_per_read || !n_reads) return hipSuccess;
+	return hipMemcpyAsync(ctx->d_n_segs, n_segs_per_read, (size_t)n_reads * 4, hipMemcpyHostToDevice, st);
+}
+
+// Profiling bracket around a launch: n events at consecutive kernel boundaries, their times added to ms[slot0...].  prof_begin
+// records the first, prof_mark the k-th; the last one queues the set for chaindp_get_kernel_ms.  Nothing happens while profiling is off.
+static hipError_t prof_begin(chaindp_ctx *ctx, EventSet &es, int n, int slot0, hipStream_t st)
+{
+	es.n = 0; es.slot0 = slot0;
+	if (!ctx->prof) return hipSuccess;
+	for (int k = 0; k < n; ++k) if (hipError_t e = hipEventCreate(&es.e[k])) return e;
+	es.n = n;
+	return hipEventRecord(es.e[0], st);
+}
+
+static hipError_t prof_mark(chaindp_ctx *ctx, EventSet &es, int k, hipStream_t st)
+{
+	if (!es.n) return hipSuccess;
+	const hipError_t e = hipEventRecord(es.e[k], st);
+	if (e == hipSuccess && k == es.n - 1) ctx->pending.push_back(es);
+	return e;
+}
 
 static Params to_params(const chaindp_params_t *p)
 {
@@ -173,15 +228,7 @@ extern "C" void chaindp_destroy(chaindp_ctx_t *ctx)
 	if (ctx->device >= 0) (void)hipSetDevice(ctx->device);
 	if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
 	for (auto &es : ctx->pending) for (int k = 0; k < es.n; ++k) (void)hipEventDestroy(es.e[k]);
-	void *bufs[] = {ctx->d_twin_queue, ctx->d_off, ctx->d_a, ctx->d_n_segs, ctx->d_f, ctx->d_p, ctx->d_v, ctx->d_tg, ctx->d_sumq, ctx->d_units,
-	                ctx->d_counters, ctx->d_unit_aux, ctx->d_left, ctx->d_left_cnt, ctx->d_deep, ctx->pre.start_mask, ctx->pre.single_mask, ctx->pre.emit_mask, ctx->pre.block_cnt, ctx->pre.tile_tmp, ctx->pre.units_tmp, ctx->pre.hist, ctx->pre.block_reads, ctx->d_lut, ctx->d_ptrs, ctx->cmp.flags, ctx->cmp.block_cnt, ctx->cmp.tile_tmp, ctx->cmp.n_seeds, ctx->cmp.sub, ctx->d_first_child, ctx->d_seeds_off, ctx->d_seeds};
-	for (void *b : bufs) if (b) (void)hipFree(b);
-	for (void *b : ctx->bot_allocs) if (b) (void)hipFree(b);
-	void *sbufs[] = {ctx->seed.kept, ctx->seed.used, ctx->seed.src, ctx->seed.mstate, ctx->seed.tile_tmp, ctx->seed.totals, ctx->seed.stacks,
-	                 ctx->d_mini, ctx->d_mini_off, ctx->d_mp_off, ctx->d_bid, ctx->d_qlen, ctx->d_rep_len, ctx->d_mini_pos};
-	for (void *b : sbufs) if (b) (void)hipFree(b);
-	for (void *b : ctx->sk_allocs) if (b) (void)hipFree(b);
-	if (ctx->d_sk_totals) (void)hipFree(ctx->d_sk_totals);
+	ctx->pool.release_all();
 	for (hipEvent_t e : ctx->sk_ev) if (e) (void)hipEventDestroy(e);
 	if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
 	delete ctx;
@@ -200,41 +247,42 @@ extern "C" chaindp_ctx_t *chaindp_create(int device, int64_t max_anchors, int64_
 	ctx->cap_anchors = max_anchors > 0 ? max_anchors : 1;
 	ctx->cap_reads = max_reads > 0 ? max_reads : 1;
 	const size_t na = (size_t)ctx->cap_anchors, nr = (size_t)ctx->cap_reads;
+	size_t flags_bytes = 0, cblocks_bytes = 0, mask_bytes = 0, blocks_bytes = 0;
+	chaindp::compact_scratch_bytes(ctx->cap_anchors, &flags_bytes, &cblocks_bytes);
+	chaindp::prepass_scratch_bytes(ctx->cap_anchors, &mask_bytes, &blocks_bytes);
 	hipError_t e = hipSetDevice(device);
 	if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_off, (nr + 1) * 8);
-	if (e == hipSuccess) e = hipMalloc(&ctx->d_a, na * 16);
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_n_segs, nr * 4);
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_f, na * 4);
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_twin_queue, 8 * 64 * sizeof(unsigned int));
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_p, na * 4);
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_v, na * 4);
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_tg, na * 8);
+	if (e == hipSuccess) e = (hipError_t)ctx->pool.alloc_group({
+		dev_buf(ctx->d_off, (nr + 1) * 8),
+		dev_buf(ctx->d_a, na * 16),
+		dev_buf(ctx->d_n_segs, nr * 4),
+		dev_buf(ctx->d_f, na * 4),
+		dev_buf(ctx->d_twin_queue, 8 * 64 * sizeof(unsigned int)),
+		dev_buf(ctx->d_p, na * 4),
+		dev_buf(ctx->d_v, na * 4),
+		dev_buf(ctx->d_tg, na * 8),
+		dev_buf(ctx->d_sumq, nr * 8),
+		dev_buf(ctx->d_units, (na / 2 + 1) * sizeof(Unit)),
+		dev_buf(ctx->d_unit_aux, (na / 2 + 1) * sizeof(chaindp::UnitAux)),
+		dev_buf(ctx->d_counters, 2 * sizeof(unsigned long long)),
+		dev_buf(ctx->d_left, (na / 2 + 1) * sizeof(Unit)),
+		dev_buf(ctx->d_left_cnt, 4 * sizeof(unsigned long long)),
+		dev_buf(ctx->d_deep, (na / 64 + 2) * sizeof(Unit)),    // a unit is handed over after its first 64-anchor tile at the earliest (test mode), with anchors to go
+		dev_buf(ctx->d_first_child, na * 4),
+		dev_buf(ctx->cmp.flags, flags_bytes),
+		dev_buf(ctx->pre.start_mask, mask_bytes),
+		dev_buf(ctx->pre.single_mask, mask_bytes),
+		dev_buf(ctx->pre.emit_mask, mask_bytes),
+		dev_buf(ctx->pre.block_cnt, blocks_bytes),
+		dev_buf(ctx->pre.tile_tmp, blocks_bytes),
+		dev_buf(ctx->pre.units_tmp, (na / 2 + 1) * sizeof(Unit)),
+		dev_buf(ctx->pre.hist, (2 * 128 + 2) * sizeof(unsigned int)),
+		dev_buf(ctx->pre.block_reads, blocks_bytes)});         // 8 B per block, like the counters
 	if (e == hipSuccess) e = hipMemset(ctx->d_tg, 0, na * 8);
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_sumq, nr * 8);
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_units, (na / 2 + 1) * sizeof(Unit));
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_unit_aux, (na / 2 + 1) * sizeof(chaindp::UnitAux));
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_counters, 2 * sizeof(unsigned long long));
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_left, (na / 2 + 1) * sizeof(Unit));
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_left_cnt, 4 * sizeof(unsigned long long));
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_deep, (na / 64 + 2) * sizeof(Unit));    // a unit is handed over after its first 64-anchor tile at the earliest (test mode), with anchors to go
-	size_t flags_bytes0 = 0, cblocks_bytes0 = 0;
-	chaindp::compact_scratch_bytes(ctx->cap_anchors, &flags_bytes0, &cblocks_bytes0);
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_first_child, na * 4);
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->cmp.flags, flags_bytes0);
-	size_t mask_bytes = 0, blocks_bytes = 0;
-	chaindp::prepass_scratch_bytes(ctx->cap_anchors, &mask_bytes, &blocks_bytes);
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->pre.start_mask, mask_bytes);
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->pre.single_mask, mask_bytes);
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->pre.emit_mask, mask_bytes);
-	ctx->cmp.single_mask = ctx->pre.single_mask; ctx->cmp.emit_mask = ctx->pre.emit_mask;
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->pre.block_cnt, blocks_bytes);
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->pre.tile_tmp, blocks_bytes);
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->pre.units_tmp, (na / 2 + 1) * sizeof(Unit));
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->pre.hist, (2 * 128 + 2) * sizeof(unsigned int));
-	ctx->pre.key_range = ctx->pre.hist ? ctx->pre.hist + 2 * 128 : nullptr;
-	if (e == hipSuccess) e = hipMalloc((void**)&ctx->pre.block_reads, blocks_bytes);   // 8 B per block, like the counters
-	ctx->cmp.block_reads = ctx->pre.block_reads;
+	if (e == hipSuccess) {                                     // aliases into the allocations above
+		ctx->cmp.single_mask = ctx->pre.single_mask; ctx->cmp.emit_mask = ctx->pre.emit_mask; ctx->cmp.block_reads = ctx->pre.block_reads;
+		ctx->pre.key_range = ctx->pre.hist + 2 * 128;
+	}
 	ctx->use_quad = getenv("CHAINDP_QUAD") != nullptr;
 	ctx->deep_handover = getenv("CHAINDP_NO_DEEP_HANDOVER") == nullptr;      // diagnostic switches are read here, once per context:
 	if (const char *v = getenv("CHAINDP_TWIN_FORCE_LEFT")) ctx->twin_force_left = atoi(v) == 2 ? 2 : 1;   // never on the launch path (contexts run from several host threads)
@@ -285,14 +333,10 @@ static int run_on_stream(chaindp_ctx *ctx, const chaindp_params_t *par, int64_t 
 	}
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	const Params q = to_params(par);
-	EventSet es; es.n = 0; es.slot0 = 0;
-	if (ctx->prof) {
-		for (int k = 0; k < 3; ++k) HIP_TRY(ctx, hipEventCreate(&es.e[k]));
-		es.n = 3;
-	}
-	if (ctx->prof) HIP_TRY(ctx, hipEventRecord(es.e[0], st));
+	EventSet es;
+	HIP_TRY(ctx, prof_begin(ctx, es, 3, 0, st));
 	HIP_TRY(ctx, chaindp::launch_prepass(st, q, n_reads, total, d_off, d_a, ctx->d_sumq, ctx->d_units, ctx->d_counters, ctx->pre, ctx->d_unit_aux, d_n_segs, ctx->d_left_cnt));
-	if (ctx->prof) HIP_TRY(ctx, hipEventRecord(es.e[1], st));
+	HIP_TRY(ctx, prof_mark(ctx, es, 1, st));
 	// per-read gap-cost table for the fast variant (skipped when the table would not apply)
 	uint16_t *lut = nullptr;
 	int lut_stride = 0;
@@ -301,10 +345,7 @@ static int run_on_stream(chaindp_ctx *ctx, const chaindp_params_t *par, int64_t 
 		const size_t need = (size_t)n_reads * lut_stride * sizeof(uint16_t);
 		if (need > ctx->lut_bytes) {
 			HIP_TRY(ctx, hipStreamSynchronize(st));
-			if (ctx->d_lut) HIP_TRY(ctx, hipFree(ctx->d_lut));
-			ctx->d_lut = nullptr; ctx->lut_bytes = 0;
-			HIP_TRY(ctx, hipMalloc((void**)&ctx->d_lut, need));
-			ctx->lut_bytes = need;
+			HIP_TRY(ctx, (hipError_t)ctx->pool.reserve((void**)&ctx->d_lut, ctx->lut_bytes, need, need, true));
 		}
 		lut = ctx->d_lut;
 		HIP_TRY(ctx, chaindp::launch_lut(st, q, n_reads, d_off, ctx->d_sumq, lut_stride, lut));
@@ -350,7 +391,7 @@ static int run_on_stream(chaindp_ctx *ctx, const chaindp_params_t *par, int64_t 
 		HIP_TRY(ctx, chaindp::launch_chain_dense1(st, q, total / 64 + 1, d_off, d_a, lut, lut_stride, ctx->d_deep, ctx->d_left_cnt + 1,
 		                                          ctx->pre.hist + CHAINDP_LONG_UNIT_CLASS, ctx->deep_route, (unsigned int*)(ctx->d_left_cnt + 2), d_f, d_p, d_v, ctx->d_first_child, ctx->cmp.flags));
 	}
-	if (ctx->prof) { HIP_TRY(ctx, hipEventRecord(es.e[2], st)); ctx->pending.push_back(es); }
+	HIP_TRY(ctx, prof_mark(ctx, es, 2, st));
 	ctx->stats[2] = total; ctx->stats[3] = n_reads;
 	return CHAINDP_OK;
 }
@@ -369,11 +410,9 @@ extern "C" int chaindp_upload(chaindp_ctx_t *ctx, int64_t n_reads, const int64_t
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_off, off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
 	if (total) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_a, a, (size_t)total * 16, hipMemcpyHostToDevice, ctx->stream));
-	ctx->has_n_segs = n_segs_per_read != nullptr;
-	if (n_segs_per_read && n_reads)
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_n_segs, n_segs_per_read, (size_t)n_reads * 4, hipMemcpyHostToDevice, ctx->stream));
+	HIP_TRY(ctx, stage_n_segs(ctx, n_segs_per_read, n_reads, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	ctx->n_reads = n_reads; ctx->total = total; ctx->ran = false; ctx->bot_n_reads = -1; ctx->mp_resident = false;
+	begin_batch(ctx, n_reads, total);
 	return CHAINDP_OK;
 }
 
@@ -447,36 +486,20 @@ static int compact_launch(chaindp_ctx *ctx, const chaindp_params_t *par)
 	if (rc) return rc;
 	if (!ctx->ran) { ctx->err = "compaction before chaindp_run"; return CHAINDP_ERR_ARG; }
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	if (!ctx->compact_ready) {
-		// first use: every buffer is allocated into a local and committed only when all of them exist, so that an
-		// out-of-memory here leaves the context as it was (the next call tries again) instead of half-initialised
-		const size_t na = (size_t)ctx->cap_anchors, nr = (size_t)ctx->cap_reads;
-		size_t flags_bytes = 0, blocks_bytes = 0;
-		chaindp::compact_scratch_bytes(ctx->cap_anchors, &flags_bytes, &blocks_bytes);
-		void *nb[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-		const size_t sz[6] = {(nr + 1) * 8, ctx->d_seeds ? 0 : na * sizeof(chaindp_seed_t) + 16, blocks_bytes, blocks_bytes, 8, blocks_bytes * 32};
-		hipError_t e = hipSuccess;
-		for (int k = 0; k < 6 && e == hipSuccess; ++k) if (sz[k]) e = hipMalloc(&nb[k], sz[k]);
-		if (e != hipSuccess) {
-			for (void *b : nb) if (b) (void)hipFree(b);
-			ctx->err = std::string("compaction buffers: ") + hipGetErrorString(e);
-			return CHAINDP_ERR_HIP;
-		}
-		ctx->d_seeds_off = (int64_t*)nb[0];
-		if (nb[1]) ctx->d_seeds = nb[1];                        // (seed collection may have made it already)
-		ctx->cmp.block_cnt = (unsigned long long*)nb[2]; ctx->cmp.tile_tmp = (unsigned long long*)nb[3];
-		ctx->cmp.n_seeds = (unsigned long long*)nb[4]; ctx->cmp.sub = (uint32_t*)nb[5];
-		ctx->compact_ready = true;
-	}
-	EventSet es; es.n = 0; es.slot0 = 2;
-	if (ctx->prof) {
-		for (int k = 0; k < 2; ++k) HIP_TRY(ctx, hipEventCreate(&es.e[k]));
-		es.n = 2;
-		HIP_TRY(ctx, hipEventRecord(es.e[0], ctx->stream));
-	}
+	const size_t na = (size_t)ctx->cap_anchors, nr = (size_t)ctx->cap_reads;
+	size_t flags_bytes = 0, blocks_bytes = 0;
+	chaindp::compact_scratch_bytes(ctx->cap_anchors, &flags_bytes, &blocks_bytes);
+	// d_seeds is the only slot of any group that may be filled before its group's first use (collect_seeds_impl makes it when it runs
+	// first): alloc_group keeps a filled slot, and a rollback frees only what this attempt allocated.  Every other slot is null here.
+	rc = first_use(ctx, ctx->compact_ready, "compaction", {
+		dev_buf(ctx->d_seeds_off, (nr + 1) * 8), dev_buf(ctx->d_seeds, na * sizeof(chaindp_seed_t) + 16),
+		dev_buf(ctx->cmp.block_cnt, blocks_bytes), dev_buf(ctx->cmp.tile_tmp, blocks_bytes), dev_buf(ctx->cmp.n_seeds, 8), dev_buf(ctx->cmp.sub, blocks_bytes * 32)});
+	if (rc) return rc;
+	EventSet es;
+	HIP_TRY(ctx, prof_begin(ctx, es, 2, 2, ctx->stream));
 	HIP_TRY(ctx, chaindp::launch_compact(ctx->stream, to_params(par), ctx->n_reads, ctx->total, ctx->d_off, ctx->d_a, ctx->d_f, ctx->d_p,
 	                                     ctx->d_v, ctx->d_first_child, ctx->d_seeds_off, ctx->d_seeds, ctx->cmp));
-	if (ctx->prof) { HIP_TRY(ctx, hipEventRecord(es.e[1], ctx->stream)); ctx->pending.push_back(es); }
+	HIP_TRY(ctx, prof_mark(ctx, es, 1, ctx->stream));
 	return CHAINDP_OK;
 }
 
@@ -489,15 +512,6 @@ static int compact_on_device(chaindp_ctx *ctx, const chaindp_params_t *par, int6
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	ctx->n_seeds = seeds_off[ctx->n_reads];
 	return CHAINDP_OK;
-}
-
-template <typename T>
-static hipError_t bot_alloc(chaindp_ctx *ctx, T *&p, size_t bytes)
-{
-	void *q = nullptr;
-	hipError_t e = hipMalloc(&q, bytes ? bytes : 8);
-	if (e == hipSuccess) { ctx->bot_allocs.push_back(q); p = (T*)q; }
-	return e;
 }
 
 extern "C" int chaindp_backtrack(chaindp_ctx_t *ctx, const chaindp_params_t *par, int min_cnt,
@@ -516,42 +530,24 @@ extern "C" int chaindp_backtrack(chaindp_ctx_t *ctx, const chaindp_params_t *par
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	const int64_t m = ctx->total > 0 && ctx->n_reads > 0 ? (int64_t)(uint32_t)n_seeds : 0;
 	ctx->n_seeds = m;
-	if (!ctx->bot_ready) {
-		// first use.  An out-of-memory half way leaves the context as it was (what this attempt allocated is freed again and the
-		// next call tries anew) instead of half-initialised with kernels launched on null scratch pointers.
-		const size_t M = (size_t)ctx->cap_anchors, R = (size_t)ctx->cap_reads, NB = M / 1024 + 2;
-		chaindp::BottomScratch &s = ctx->bot;
-		const size_t first = ctx->bot_allocs.size();
-		hipError_t e = hipSuccess;
-#define BOT_ALLOC(field, bytes) if (e == hipSuccess) e = bot_alloc(ctx, s.field, (bytes))
-		BOT_ALLOC(has, M);
-		BOT_ALLOC(owner, M * 4); BOT_ALLOC(end_rec, M * 4); BOT_ALLOC(ccnt, M * 4); BOT_ALLOC(kpos, M * 4); BOT_ALLOC(bpos, M * 4);
-		BOT_ALLOC(c_src, M * 4); BOT_ALLOC(c_dst, M * 4);
-		BOT_ALLOC(key, M * 8); BOT_ALLOC(skey, M * 8); BOT_ALLOC(cu, M * 8); BOT_ALLOC(u_tmp, M * 8); BOT_ALLOC(u_out, M * 8);
-		BOT_ALLOC(b_tmp, M * 16); BOT_ALLOC(b_out, M * 16); BOT_ALLOC(w, M * 16);
-		BOT_ALLOC(stacks, (M / 64 + 2 * R + 4) * 12);
-		BOT_ALLOC(block_cnt, (NB > R + 2 ? NB : R + 2) * 8); BOT_ALLOC(tile_tmp, (NB > R + 2 ? NB : R + 2) * 8);
-		BOT_ALLOC(read_tot, (R + 2) * 8); BOT_ALLOC(total, 8);
-		BOT_ALLOC(ends_off, (R + 2) * 8); BOT_ALLOC(chains_off, (R + 2) * 8); BOT_ALLOC(b_off, (R + 2) * 8);
-#undef BOT_ALLOC
-		if (e != hipSuccess) {
-			for (size_t k = first; k < ctx->bot_allocs.size(); ++k) if (ctx->bot_allocs[k]) (void)hipFree(ctx->bot_allocs[k]);
-			ctx->bot_allocs.resize(first);
-			ctx->bot = chaindp::BottomScratch{};
-			ctx->err = std::string("backtrack buffers: ") + hipGetErrorString(e);
-			return CHAINDP_ERR_HIP;
-		}
-		ctx->bot_ready = true;
-	}
-	EventSet es; es.n = 0; es.slot0 = 3;
-	if (ctx->prof) {
-		for (int k = 0; k < 2; ++k) HIP_TRY(ctx, hipEventCreate(&es.e[k]));
-		es.n = 2;
-		HIP_TRY(ctx, hipEventRecord(es.e[0], ctx->stream));
-	}
+	const size_t M = (size_t)ctx->cap_anchors, R = (size_t)ctx->cap_reads, NB = M / 1024 + 2, NS = (NB > R + 2 ? NB : R + 2) * 8;
+	chaindp::BottomScratch &s = ctx->bot;
+	rc = first_use(ctx, ctx->bot_ready, "backtrack", {
+		dev_buf(s.has, M),
+		dev_buf(s.owner, M * 4), dev_buf(s.end_rec, M * 4), dev_buf(s.ccnt, M * 4), dev_buf(s.kpos, M * 4), dev_buf(s.bpos, M * 4),
+		dev_buf(s.c_src, M * 4), dev_buf(s.c_dst, M * 4),
+		dev_buf(s.key, M * 8), dev_buf(s.skey, M * 8), dev_buf(s.cu, M * 8), dev_buf(s.u_tmp, M * 8), dev_buf(s.u_out, M * 8),
+		dev_buf(s.b_tmp, M * 16), dev_buf(s.b_out, M * 16), dev_buf(s.w, M * 16),
+		dev_buf(s.stacks, (M / 64 + 2 * R + 4) * 12),
+		dev_buf(s.block_cnt, NS), dev_buf(s.tile_tmp, NS),
+		dev_buf(s.read_tot, (R + 2) * 8), dev_buf(s.total, 8),
+		dev_buf(s.ends_off, (R + 2) * 8), dev_buf(s.chains_off, (R + 2) * 8), dev_buf(s.b_off, (R + 2) * 8)});
+	if (rc) return rc;
+	EventSet es;
+	HIP_TRY(ctx, prof_begin(ctx, es, 2, 3, ctx->stream));
 	HIP_TRY(ctx, chaindp::launch_backtrack(ctx->stream, min_cnt, par->min_sc, ctx->n_reads, ctx->cap_anchors, ctx->d_seeds_off, ctx->d_seeds,
 	                                       ctx->cmp.n_seeds, ctx->bot, m));
-	if (ctx->prof) { HIP_TRY(ctx, hipEventRecord(es.e[1], ctx->stream)); ctx->pending.push_back(es); }
+	HIP_TRY(ctx, prof_mark(ctx, es, 1, ctx->stream));
 	const size_t ob = (size_t)(ctx->n_reads > 0 ? ctx->n_reads + 1 : 1) * 8;
 	HIP_TRY(ctx, hipMemcpyAsync(chains_off, ctx->bot.chains_off, ob, hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(ctx, hipMemcpyAsync(b_off, ctx->bot.b_off, ob, hipMemcpyDeviceToHost, ctx->stream));
@@ -564,26 +560,40 @@ extern "C" int chaindp_backtrack(chaindp_ctx_t *ctx, const chaindp_params_t *par
 	return CHAINDP_OK;
 }
 
-// grow-only device buffer owned by the context (freed with the backtrack allocations)
-static hipError_t regs_grow(chaindp_ctx *ctx, void *&p, size_t &cap, size_t need)
-{
-	if (need <= cap && p) return hipSuccess;
-	void *q = nullptr;
-	hipError_t e = hipMalloc(&q, need ? need + need / 4 : 8);
-	if (e != hipSuccess) return e;
-	for (void *&old : ctx->bot_allocs) if (old == p && p) { (void)hipFree(p); old = nullptr; }
-	ctx->bot_allocs.push_back(q);
-	p = q; cap = need + need / 4;
-	return hipSuccess;
-}
-
+// per-read arrays of the hit stages
 static int regs_per_read_buffers(chaindp_ctx *ctx)
 {
-	if (ctx->d_rhash) return CHAINDP_OK;
 	const size_t R = (size_t)ctx->cap_reads + 2;
-	HIP_TRY(ctx, bot_alloc(ctx, ctx->d_rhash, R * 4)); HIP_TRY(ctx, bot_alloc(ctx, ctx->d_rqlen, R * 4));
-	HIP_TRY(ctx, bot_alloc(ctx, ctx->d_regs_off, R * 8)); HIP_TRY(ctx, bot_alloc(ctx, ctx->d_mp_off_up, R * 8));
-	HIP_TRY(ctx, bot_alloc(ctx, ctx->d_sum_k, R * 8));
+	return first_use(ctx, ctx->regs_ready, "hit", {dev_buf(ctx->d_rhash, R * 4), dev_buf(ctx->d_rqlen, R * 4), dev_buf(ctx->d_regs_off, R * 8),
+	                                               dev_buf(ctx->d_mp_off_up, R * 8), dev_buf(ctx->d_sum_k, R * 8)});
+}
+
+// mini_pos[] of the batch for mm_est_err: the caller's arrays or, with both NULL, what chaindp_collect_seeds left resident.
+// mini_pos_check is the argument check (no device work); stage_mini_pos uploads the caller's arrays and the targets' lengths,
+// growing their buffers, and returns the offsets and positions the kernel reads.
+static int mini_pos_check(chaindp_ctx *ctx, const int64_t *mini_pos_off, const uint64_t *mini_pos)
+{
+	const bool resident = mini_pos == nullptr && mini_pos_off == nullptr;
+	if (resident && (!ctx->mp_resident || !ctx->d_mp_off)) { ctx->err = "no resident mini_pos: pass the arrays, or collect the seeds with chaindp_collect_seeds"; return CHAINDP_ERR_ARG; }
+	if (!resident && !mini_pos_off) { ctx->err = "mini_pos without offsets"; return CHAINDP_ERR_ARG; }
+	return CHAINDP_OK;
+}
+
+static int stage_mini_pos(chaindp_ctx *ctx, int64_t R, const int64_t *mini_pos_off, const uint64_t *mini_pos, const int32_t *ref_len, int32_t n_ref,
+                          const int64_t *&d_mpo, const unsigned long long *&d_mp)
+{
+	hipStream_t st = ctx->stream;
+	d_mpo = ctx->d_mp_off; d_mp = ctx->d_mini_pos;
+	if (mini_pos || mini_pos_off) {
+		const int64_t n_mp = mini_pos_off[R];
+		if (n_mp < 0 || (n_mp > 0 && !mini_pos)) { ctx->err = "mini_pos announced but absent"; return CHAINDP_ERR_ARG; }
+		HIP_TRY(ctx, dev_grow(ctx, ctx->d_mp_up, ctx->mp_up_cap, (size_t)(n_mp > 0 ? n_mp : 1) * 8));
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mp_off_up, mini_pos_off, (size_t)(R + 1) * 8, hipMemcpyHostToDevice, st));
+		if (n_mp > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mp_up, mini_pos, (size_t)n_mp * 8, hipMemcpyHostToDevice, st));
+		d_mpo = ctx->d_mp_off_up; d_mp = (const unsigned long long*)ctx->d_mp_up;
+	}
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_ref_len, ctx->ref_len_cap, (size_t)(n_ref > 0 ? n_ref : 1) * 4));
+	if (n_ref > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ref_len, ref_len, (size_t)n_ref * 4, hipMemcpyHostToDevice, st));
 	return CHAINDP_OK;
 }
 
@@ -600,7 +610,7 @@ static int gen_regs_impl(chaindp_ctx *ctx, const uint32_t *hash, const int32_t *
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	int rc = regs_per_read_buffers(ctx);
 	if (rc) return rc;
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_regs, ctx->regs_cap, (size_t)n_c * sizeof(chaindp_reg_t)));
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_regs, ctx->regs_cap, (size_t)n_c * sizeof(chaindp_reg_t)));
 	hipStream_t st = ctx->stream;
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rhash, hash, (size_t)R * 4, hipMemcpyHostToDevice, st));
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rqlen, qlen, (size_t)R * 4, hipMemcpyHostToDevice, st));
@@ -632,13 +642,11 @@ extern "C" int chaindp_est_err(chaindp_ctx_t *ctx, const int64_t *regs_off, chai
 	const int64_t n_regs = regs_off[R];
 	if (n_regs == 0) return CHAINDP_OK;
 	if (!regs) { ctx->err = "NULL regs"; return CHAINDP_ERR_ARG; }
-	const bool resident = mini_pos == nullptr && mini_pos_off == nullptr;
-	if (resident && (!ctx->mp_resident || !ctx->d_mp_off)) { ctx->err = "no resident mini_pos: pass the arrays, or collect the seeds with chaindp_collect_seeds"; return CHAINDP_ERR_ARG; }
-	if (!resident && !mini_pos_off) { ctx->err = "mini_pos without offsets"; return CHAINDP_ERR_ARG; }
+	int rc = mini_pos_check(ctx, mini_pos_off, mini_pos);
+	if (rc) return rc;
 	for (int64_t g = 0; g < n_regs; ++g) if (regs[g].cnt < 0 || regs[g].as < 0) { ctx->err = "hit with a negative count or offset"; return CHAINDP_ERR_ARG; }
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	int rc = regs_per_read_buffers(ctx);
-	if (rc) return rc;
+	if ((rc = regs_per_read_buffers(ctx)) != CHAINDP_OK) return rc;
 	hipStream_t st = ctx->stream;
 	ctx->regs_resident = false;                                  // the upload below replaces what chaindp_gen_regs left in d_regs / d_rqlen
 	// every hit's anchors must lie inside its read's chain anchors: checked here, on the host's copy of the offsets
@@ -650,22 +658,13 @@ extern "C" int chaindp_est_err(chaindp_ctx_t *ctx, const int64_t *regs_off, chai
 			for (int64_t g = regs_off[r]; g < regs_off[r + 1]; ++g)
 				if ((int64_t)regs[g].as + regs[g].cnt > boff[r + 1] - boff[r]) { ctx->err = "hit reaches beyond its read's chain anchors"; return CHAINDP_ERR_ARG; }
 	}
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_regs, ctx->regs_cap, (size_t)n_regs * sizeof(chaindp_reg_t)));
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_reg_counts, ctx->reg_counts_cap, (size_t)n_regs * 8));
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_ref_len, ctx->ref_len_cap, (size_t)(n_ref > 0 ? n_ref : 1) * 4));
-	const int64_t *d_mpo = ctx->d_mp_off;
-	const unsigned long long *d_mp = ctx->d_mini_pos;
-	if (!resident) {
-		const int64_t n_mp = mini_pos_off[R];
-		if (n_mp < 0 || (n_mp > 0 && !mini_pos)) { ctx->err = "mini_pos announced but absent"; return CHAINDP_ERR_ARG; }
-		HIP_TRY(ctx, regs_grow(ctx, ctx->d_mp_up, ctx->mp_up_cap, (size_t)(n_mp > 0 ? n_mp : 1) * 8));
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mp_off_up, mini_pos_off, (size_t)(R + 1) * 8, hipMemcpyHostToDevice, st));
-		if (n_mp > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mp_up, mini_pos, (size_t)n_mp * 8, hipMemcpyHostToDevice, st));
-		d_mpo = ctx->d_mp_off_up; d_mp = (const unsigned long long*)ctx->d_mp_up;
-	}
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_regs, ctx->regs_cap, (size_t)n_regs * sizeof(chaindp_reg_t)));
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_reg_counts, ctx->reg_counts_cap, (size_t)n_regs * 8));
+	const int64_t *d_mpo = nullptr;
+	const unsigned long long *d_mp = nullptr;
+	if ((rc = stage_mini_pos(ctx, R, mini_pos_off, mini_pos, ref_len, n_ref, d_mpo, d_mp)) != CHAINDP_OK) return rc;
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_regs_off, regs_off, (size_t)(R + 1) * 8, hipMemcpyHostToDevice, st));
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_rqlen, qlen, (size_t)R * 4, hipMemcpyHostToDevice, st));
-	if (n_ref > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ref_len, ref_len, (size_t)n_ref * 4, hipMemcpyHostToDevice, st));
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_regs, regs, (size_t)n_regs * sizeof(chaindp_reg_t), hipMemcpyHostToDevice, st));
 	HIP_TRY(ctx, chaindp::launch_est_err(st, R, n_regs, ctx->d_regs_off, ctx->bot.b_off, ctx->bot.b_out, ctx->d_rqlen, (const int32_t*)ctx->d_ref_len, n_ref,
 	                                     d_mpo, d_mp, ctx->d_sum_k, ctx->d_regs, (int32_t*)ctx->d_reg_counts));
@@ -763,14 +762,8 @@ extern "C" int64_t chaindp_debug_deep_units(chaindp_ctx_t *ctx)
 	return (int64_t)(uint32_t)c;
 }
 
-// test hook (not in the public header): fills one of the backtrack allocations (in allocation order) with a byte
-extern "C" int chaindp_debug_poison(chaindp_ctx_t *ctx, int which, int byte, size_t bytes)
-{
-	if (!ctx || which < 0 || (size_t)which >= ctx->bot_allocs.size()) return CHAINDP_ERR_ARG;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	HIP_TRY(ctx, hipMemset(ctx->bot_allocs[which], byte, bytes));
-	return CHAINDP_OK;
-}
+// test hook (not in the public header): bytes of device memory the context owns at this moment
+extern "C" int64_t chaindp_debug_device_bytes(chaindp_ctx_t *ctx) { return ctx ? (int64_t)ctx->pool.bytes() : -1; }
 
 // test hook (not in the public header): copies one of the backtrack scratch arrays to the host
 extern "C" int chaindp_debug_bottom(chaindp_ctx_t *ctx, int which, void *dst, size_t bytes)
@@ -837,13 +830,10 @@ extern "C" int chaindp_compact(chaindp_ctx_t *ctx, const chaindp_params_t *par, 
 // device array of n_reads host pointers (grown on demand)
 static int stage_pointers(chaindp_ctx *ctx, const void *const *ptrs, int64_t n)
 {
-	if ((size_t)n > ctx->ptr_cap) {
+	if ((size_t)n * sizeof(void*) > ctx->ptr_bytes) {
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		if (ctx->d_ptrs) HIP_TRY(ctx, hipFree(ctx->d_ptrs));
-		ctx->d_ptrs = nullptr; ctx->ptr_cap = 0;
 		const size_t cap = (size_t)n + (size_t)n / 2 + 64;
-		HIP_TRY(ctx, hipMalloc((void**)&ctx->d_ptrs, cap * sizeof(void*)));
-		ctx->ptr_cap = cap;
+		HIP_TRY(ctx, (hipError_t)ctx->pool.reserve((void**)&ctx->d_ptrs, ctx->ptr_bytes, (size_t)n * sizeof(void*), cap * sizeof(void*), true));
 	}
 	if (n) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ptrs, ptrs, (size_t)n * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
 	return CHAINDP_OK;
@@ -867,11 +857,9 @@ extern "C" int chaindp_upload_gather_ex(chaindp_ctx_t *ctx, int64_t n_reads, con
 	int rc = stage_pointers(ctx, (const void *const *)read_anchors, n_reads);
 	if (rc) return rc;
 	HIP_TRY(ctx, chaindp::launch_gather_reads(ctx->stream, n_reads, ctx->d_off, (const void *const *)ctx->d_ptrs, ctx->d_a));
-	ctx->has_n_segs = n_segs_per_read != nullptr;
-	if (n_segs_per_read && n_reads)
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_n_segs, n_segs_per_read, (size_t)n_reads * 4, hipMemcpyHostToDevice, ctx->stream));
+	HIP_TRY(ctx, stage_n_segs(ctx, n_segs_per_read, n_reads, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));       // the host arrays (off, pointers) may go away after the call
-	ctx->n_reads = n_reads; ctx->total = total; ctx->ran = false; ctx->bot_n_reads = -1; ctx->mp_resident = false;
+	begin_batch(ctx, n_reads, total);
 	return CHAINDP_OK;
 }
 
@@ -904,11 +892,9 @@ extern "C" int chaindp_upload_gather(chaindp_ctx_t *ctx, int64_t n_reads, const 
 		if (n < 0 || (n > 0 && !read_anchors[r])) { ctx->err = "bad read in gather list"; return CHAINDP_ERR_ARG; }
 		if (n) HIP_TRY(ctx, hipMemcpyAsync((chaindp_anchor_t*)ctx->d_a + off[r], read_anchors[r], (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
 	}
-	ctx->has_n_segs = n_segs_per_read != nullptr;
-	if (n_segs_per_read && n_reads)
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_n_segs, n_segs_per_read, (size_t)n_reads * 4, hipMemcpyHostToDevice, ctx->stream));
+	HIP_TRY(ctx, stage_n_segs(ctx, n_segs_per_read, n_reads, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	ctx->n_reads = n_reads; ctx->total = total; ctx->ran = false; ctx->bot_n_reads = -1; ctx->mp_resident = false;
+	begin_batch(ctx, n_reads, total);
 	return CHAINDP_OK;
 }
 
@@ -1003,39 +989,25 @@ extern "C" void chaindp_index_destroy(chaindp_index_t *ix)
 // with every one of them released, so that the next call starts from nothing
 static int seed_reserve(chaindp_ctx *ctx, int64_t n_mini, bool oom_is_capacity = false)
 {
-	if (!ctx->seed_ready) {
-		// first use: all or nothing, as in compact_launch
-		const size_t nr = (size_t)ctx->cap_reads;
-		void **slot[7] = {(void**)&ctx->d_mini_off, (void**)&ctx->d_mp_off, (void**)&ctx->d_bid, (void**)&ctx->d_qlen, (void**)&ctx->d_rep_len,
-		                  (void**)&ctx->seed.totals, (void**)&ctx->seed.stacks};
-		const size_t stack_bytes = ((size_t)ctx->cap_anchors / 64 + 2 * nr + 4) * 12, tied_bytes = ((size_t)ctx->cap_anchors / 64 + nr + 8) * 4;
-		const size_t sz[7] = {(nr + 1) * 8, (nr + 1) * 8, (nr + 1) * 4, (nr + 1) * 4, (nr + 1) * 4, 32, stack_bytes + tied_bytes};
-		void *nb[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-		hipError_t e = hipSuccess;
-		for (int k = 0; k < 7 && e == hipSuccess; ++k) e = hipMalloc(&nb[k], sz[k]);
-		if (e != hipSuccess) {
-			for (void *q : nb) if (q) (void)hipFree(q);
-			ctx->err = std::string("seed collection buffers: ") + hipGetErrorString(e);
-			return CHAINDP_ERR_HIP;
-		}
-		for (int k = 0; k < 7; ++k) *slot[k] = nb[k];
-		ctx->seed.tied = (uint32_t*)((char*)ctx->seed.stacks + stack_bytes);
-		ctx->seed_ready = true;
-	}
+	const size_t nr = (size_t)ctx->cap_reads;
+	const size_t stack_bytes = ((size_t)ctx->cap_anchors / 64 + 2 * nr + 4) * 12, tied_bytes = ((size_t)ctx->cap_anchors / 64 + nr + 8) * 4;
+	const int rc = first_use(ctx, ctx->seed_ready, "seed collection", {
+		dev_buf(ctx->d_mini_off, (nr + 1) * 8), dev_buf(ctx->d_mp_off, (nr + 1) * 8), dev_buf(ctx->d_bid, (nr + 1) * 4), dev_buf(ctx->d_qlen, (nr + 1) * 4),
+		dev_buf(ctx->d_rep_len, (nr + 1) * 4), dev_buf(ctx->seed.totals, 32), dev_buf(ctx->seed.stacks, stack_bytes + tied_bytes)});
+	if (rc) return rc;
+	ctx->seed.tied = (uint32_t*)((char*)ctx->seed.stacks + stack_bytes);   // (an alias into stacks, not an allocation)
 	if (n_mini > ctx->seed_cap_mini) {
+		// the per-minimizer buffers grow together: release, then allocate (a lower peak), all of them or none
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		void **grow[] = {(void**)&ctx->seed.kept, (void**)&ctx->seed.used, (void**)&ctx->seed.src, (void**)&ctx->seed.mstate,
-		                 (void**)&ctx->seed.tile_tmp, (void**)&ctx->d_mini, (void**)&ctx->d_mini_pos};
-		for (void **g : grow) if (*g) { HIP_TRY(ctx, hipFree(*g)); *g = nullptr; }
-		ctx->seed_cap_mini = 0;
 		const size_t n = (size_t)n_mini + (size_t)n_mini / 4 + 1024;
-		const size_t each[7] = {n * 8, n * 8, n * 8, n * 8, (n / 1024 + 2) * 8, n * 16, n * 8};
-		for (int k = 0; k < 7; ++k) {
-			const hipError_t e = hipMalloc(grow[k], each[k]);
-			if (e == hipSuccess) continue;
-			if (!oom_is_capacity) { ctx->err = std::string("hipMalloc (seed collection buffers): ") + hipGetErrorString(e); return CHAINDP_ERR_HIP; }
+		const chaindp::DevBuf grow[7] = {dev_buf(ctx->seed.kept, n * 8), dev_buf(ctx->seed.used, n * 8), dev_buf(ctx->seed.src, n * 8), dev_buf(ctx->seed.mstate, n * 8),
+		                                 dev_buf(ctx->seed.tile_tmp, (n / 1024 + 2) * 8), dev_buf(ctx->d_mini, n * 16), dev_buf(ctx->d_mini_pos, n * 8)};
+		for (const chaindp::DevBuf &g : grow) ctx->pool.release(g.slot);
+		ctx->seed_cap_mini = 0;
+		const hipError_t e = (hipError_t)ctx->pool.alloc_group(grow, 7);
+		if (e != hipSuccess && !oom_is_capacity) { ctx->err = std::string("hipMalloc (seed collection buffers): ") + hipGetErrorString(e); return CHAINDP_ERR_HIP; }
+		if (e != hipSuccess) {
 			(void)hipGetLastError();
-			for (void **g : grow) if (*g) { (void)hipFree(*g); *g = nullptr; }
 			ctx->err = std::string("minimizer buffers for ") + std::to_string((long long)n_mini) + " minimizers: " + hipGetErrorString(e);
 			return CHAINDP_ERR_CAPACITY;
 		}
@@ -1081,8 +1053,7 @@ static int collect_seeds_impl(chaindp_ctx *ctx, const chaindp_index_t *ix, int f
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bid, bid, (size_t)n_reads * 4, hipMemcpyHostToDevice, st));
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_qlen, qlen, (size_t)n_reads * 4, hipMemcpyHostToDevice, st));
 	}
-	ctx->has_n_segs = n_segs_per_read != nullptr;
-	if (n_segs_per_read && n_reads) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_n_segs, n_segs_per_read, (size_t)n_reads * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, stage_n_segs(ctx, n_segs_per_read, n_reads, st));
 	chaindp::SeedIndex dix;
 	dix.B = ix->blob[0]; dix.H = ix->blob[1]; dix.V = ix->blob[2]; dix.P = ix->blob[3];
 	dix.nB = ix->bytes[0]; dix.nH = ix->bytes[1]; dix.nV = ix->bytes[2]; dix.nP = ix->bytes[3];
@@ -1093,12 +1064,12 @@ static int collect_seeds_impl(chaindp_ctx *ctx, const chaindp_index_t *ix, int f
 	HIP_TRY(ctx, hipMemcpyAsync(totals, ctx->seed.totals, 16, hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipStreamSynchronize(st));
 	if ((int64_t)totals[0] > ctx->cap_anchors) {
-		ctx->n_reads = 0; ctx->total = 0; ctx->ran = false; ctx->bot_n_reads = -1; ctx->mp_resident = false;
+		begin_batch(ctx, 0, 0);
 		ctx->err = "the batch's seeds exceed the anchor capacity the context was created with";
 		return CHAINDP_ERR_CAPACITY;
 	}
 	// unsorted anchors go to the new_seed[] buffer (free at this point of a batch), the sort writes d_a
-	if (!ctx->d_seeds) HIP_TRY(ctx, hipMalloc(&ctx->d_seeds, (size_t)ctx->cap_anchors * sizeof(chaindp_seed_t) + 16));
+	if (!ctx->d_seeds) HIP_TRY(ctx, (hipError_t)ctx->pool.alloc(&ctx->d_seeds, (size_t)ctx->cap_anchors * sizeof(chaindp_seed_t) + 16));
 	if (ctx->seed_max_n < 0) {
 		int lds_limit = 0;
 		HIP_TRY(ctx, hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
@@ -1120,7 +1091,8 @@ static int collect_seeds_impl(chaindp_ctx *ctx, const chaindp_index_t *ix, int f
 	if (mini_pos_off) HIP_TRY(ctx, hipMemcpyAsync(mini_pos_off, ctx->d_mp_off, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
 	if (rep_len && n_reads) HIP_TRY(ctx, hipMemcpyAsync(rep_len, ctx->d_rep_len, (size_t)n_reads * 4, hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipStreamSynchronize(st));
-	ctx->n_reads = n_reads; ctx->total = (int64_t)totals[0]; ctx->n_mini_pos = (int64_t)totals[1]; ctx->ran = false; ctx->bot_n_reads = -1; ctx->mp_resident = true;
+	begin_batch(ctx, n_reads, (int64_t)totals[0], true);
+	ctx->n_mini_pos = (int64_t)totals[1];
 	return CHAINDP_OK;
 }
 
@@ -1140,6 +1112,28 @@ extern "C" int chaindp_collect_seeds_gather(chaindp_ctx_t *ctx, const chaindp_in
 	return collect_seeds_impl(ctx, ix, flag, max_occ, n_reads, mini_off, nullptr, read_mini, bid, qlen, n_segs_per_read, off, rep_len, mini_pos_off);
 }
 
+// What the map calls open with: seeds (resident), DP + compaction, chains, hits -- every stage reads what the one before left in HBM.
+// regs_off != NULL (chaindp_map_batch): the chain offsets go there and the hits are downloaded to regs, if regs_cap has room for them;
+// NULL: the hits stay in HBM for the post steps.  A NULL qlen with NULL minimizers means the resident sketch's (checked by the seed
+// collection); the caller gets it back.
+static int map_prefix(chaindp_ctx *ctx, const chaindp_index_t *ix, int flag, int max_occ, const chaindp_params_t *par, int min_cnt, int64_t n_reads,
+                      const int64_t *mini_off, const chaindp_anchor_t *mini, const uint32_t *bid, const int32_t *&qlen, const int32_t *n_segs_per_read,
+                      const uint32_t *hash, int32_t *rep_len, int64_t *n_anchors, int64_t *regs_off, chaindp_reg_t *regs, int64_t regs_cap)
+{
+	if (!mini && !mini_off && !qlen && ctx->sk_valid && n_reads == ctx->sk_n_reads) qlen = ctx->sk_qlen.data();
+	int rc = collect_seeds_impl(ctx, ix, flag, max_occ, n_reads, mini_off, mini, nullptr, bid, qlen, n_segs_per_read, nullptr, rep_len, nullptr);
+	if (rc) return rc;
+	if (n_anchors) *n_anchors = ctx->total;
+	if ((rc = chaindp_run_full(ctx, par)) != CHAINDP_OK) return rc;
+	std::vector<int64_t> c_off((size_t)(regs_off || n_reads <= 0 ? 1 : n_reads + 1)), b_off((size_t)(n_reads > 0 ? n_reads + 1 : 1));
+	if ((rc = chaindp_backtrack(ctx, par, min_cnt, regs_off ? regs_off : c_off.data(), nullptr, b_off.data(), nullptr)) != CHAINDP_OK) return rc;
+	if (regs_off && (n_reads > 0 ? regs_off[n_reads] : 0) > regs_cap) {
+		ctx->err = "more hits than regs has room for (regs_off is valid; chaindp_gen_regs with a larger buffer returns them)";
+		return CHAINDP_ERR_CAPACITY;
+	}
+	return gen_regs_impl(ctx, hash, qlen, regs, regs_off != nullptr);
+}
+
 extern "C" int chaindp_map_batch(chaindp_ctx_t *ctx, const chaindp_index_t *ix, int flag, int max_occ, const chaindp_params_t *par, int min_cnt,
                                  int64_t n_reads, const int64_t *mini_off, const chaindp_anchor_t *mini, const uint32_t *bid, const int32_t *qlen,
                                  const uint32_t *hash, int64_t *regs_off, chaindp_reg_t *regs, int64_t regs_cap, int32_t *rep_len, int64_t *n_anchors)
@@ -1148,16 +1142,7 @@ extern "C" int chaindp_map_batch(chaindp_ctx_t *ctx, const chaindp_index_t *ix, 
 	int rc = check_params(ctx, par);
 	if (rc) return rc;
 	if (!regs_off || regs_cap < 0 || (regs_cap > 0 && !regs) || (n_reads > 0 && !hash)) { ctx->err = "NULL output or hash"; return CHAINDP_ERR_ARG; }
-	if (!mini && !mini_off && !qlen && ctx->sk_valid && n_reads == ctx->sk_n_reads) qlen = ctx->sk_qlen.data();   // the resident sketch's (checked below)
-	// seeds (resident), DP + compaction, chains, hits: every stage reads what the one before left in HBM
-	if ((rc = collect_seeds_impl(ctx, ix, flag, max_occ, n_reads, mini_off, mini, nullptr, bid, qlen, nullptr, nullptr, rep_len, nullptr)) != CHAINDP_OK) return rc;
-	if (n_anchors) *n_anchors = ctx->total;
-	if ((rc = chaindp_run_full(ctx, par)) != CHAINDP_OK) return rc;
-	std::vector<int64_t> b_off((size_t)(n_reads > 0 ? n_reads + 1 : 1));
-	if ((rc = chaindp_backtrack(ctx, par, min_cnt, regs_off, nullptr, b_off.data(), nullptr)) != CHAINDP_OK) return rc;
-	const int64_t n_c = n_reads > 0 ? regs_off[n_reads] : 0;
-	if (n_c > regs_cap) { ctx->err = "more hits than regs has room for (regs_off is valid; chaindp_gen_regs with a larger buffer returns them)"; return CHAINDP_ERR_CAPACITY; }
-	return chaindp_gen_regs(ctx, hash, qlen, regs);
+	return map_prefix(ctx, ix, flag, max_occ, par, min_cnt, n_reads, mini_off, mini, bid, qlen, nullptr, hash, rep_len, n_anchors, regs_off, regs, regs_cap);
 }
 
 extern "C" int chaindp_scatter_mini_pos(chaindp_ctx_t *ctx, int64_t n_reads, uint64_t *const *dst)
@@ -1192,62 +1177,47 @@ extern "C" int chaindp_download_anchors(chaindp_ctx_t *ctx, chaindp_anchor_t *a)
 
 // ---- sketch on the GPU (include/chaindp.h): bases in, minimizers resident
 
-template <typename T>
-static hipError_t sk_alloc(chaindp_ctx *ctx, T *&p, size_t bytes)
-{
-	void *q = nullptr;
-	hipError_t e = hipMalloc(&q, bytes ? bytes : 8);
-	if (e == hipSuccess) { ctx->sk_allocs.push_back(q); p = (T*)q; }
-	return e;
-}
-
 // Buffers for a batch of n_bases bases in n_chunks chunks of n_seqs sequences.  All or nothing: when an allocation fails everything
 // is released, so that the context is as it was before its first sketch.
 static int sketch_reserve(chaindp_ctx *ctx, int64_t n_bases, int64_t n_chunks, int64_t n_seqs)
 {
-	if (!ctx->d_sk_totals) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_sk_totals, 4 * 8));
+	if (!ctx->d_sk_totals) HIP_TRY(ctx, (hipError_t)ctx->pool.alloc((void**)&ctx->d_sk_totals, 4 * 8));
 	if (n_bases <= ctx->sk_cap_bases && n_chunks <= ctx->sk_cap_chunks && n_seqs <= ctx->sk_cap_seqs) return CHAINDP_OK;
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	for (void *b : ctx->sk_allocs) if (b) (void)hipFree(b);
-	ctx->sk_allocs.clear();
-	ctx->sk = {};
-	ctx->sk_cap_bases = ctx->sk_cap_chunks = ctx->sk_cap_seqs = -1;
 	const size_t nb = (size_t)n_bases + (size_t)n_bases / 8 + 1024, nc = (size_t)n_chunks + (size_t)n_chunks / 8 + 64, nq = (size_t)n_seqs + (size_t)n_seqs / 8 + 64;
 	const size_t nt = nb / 256 + 2, nr = (size_t)ctx->cap_reads + 2;
 	size_t scan_items = nc + 1 > nt ? nc + 1 : nt;
 	if (nr > scan_items) scan_items = nr;
 	chaindp::SketchArgs &k = ctx->sk;
-	uint8_t *d_seq = nullptr; int64_t *d_seq_off = nullptr; int32_t *d_chunk_seq = nullptr, *d_seq_chunk0 = nullptr, *d_read_seq0 = nullptr;
-	unsigned long long *d_ybase = nullptr;
-	hipError_t e = sk_alloc(ctx, d_seq, nb + 16);
-	if (e == hipSuccess) e = sk_alloc(ctx, d_seq_off, (nq + 1) * 8);
-	if (e == hipSuccess) e = sk_alloc(ctx, d_chunk_seq, nc * 4);
-	if (e == hipSuccess) e = sk_alloc(ctx, d_seq_chunk0, (nq + 1) * 4);
-	if (e == hipSuccess) e = sk_alloc(ctx, d_read_seq0, nr * 4);
-	if (e == hipSuccess) e = sk_alloc(ctx, d_ybase, nq * 8);
-	if (e == hipSuccess) e = sk_alloc(ctx, k.chunk_push, (nc + 1) * 8);
-	if (e == hipSuccess) e = sk_alloc(ctx, k.chunk_slot, (nc + 1) * 8);
-	if (e == hipSuccess) e = sk_alloc(ctx, k.tile_cnt, nt * 8);
-	if (e == hipSuccess) e = sk_alloc(ctx, k.scan_tmp, (scan_items / 1024 + 4) * 8);
-	if (e == hipSuccess) e = sk_alloc(ctx, k.pcode, nb + 16);
-	if (e == hipSuccess) e = sk_alloc(ctx, k.pstart, nb * 4);
-	if (e == hipSuccess) e = sk_alloc(ctx, k.pend, nb * 4);
-	if (e == hipSuccess) e = sk_alloc(ctx, k.phz, nb * 8);
-	if (e == hipSuccess) e = sk_alloc(ctx, k.sx, nb * 8);
-	if (e == hipSuccess) e = sk_alloc(ctx, k.sy, nb * 8);
-	if (e == hipSuccess) e = sk_alloc(ctx, k.sn, nb + 16);
-	if (e == hipSuccess) e = sk_alloc(ctx, k.slc, nb);
-	if (e == hipSuccess) e = sk_alloc(ctx, k.sseq, nb * 4);
-	if (e == hipSuccess) e = sk_alloc(ctx, k.scnt, nb * 4);
+	const chaindp::DevBuf bufs[20] = {
+		dev_buf(k.seq, nb + 16),
+		dev_buf(k.seq_off, (nq + 1) * 8),
+		dev_buf(k.chunk_seq, nc * 4),
+		dev_buf(k.seq_chunk0, (nq + 1) * 4),
+		dev_buf(k.read_seq0, nr * 4),
+		dev_buf(k.seq_ybase, nq * 8),
+		dev_buf(k.chunk_push, (nc + 1) * 8),
+		dev_buf(k.chunk_slot, (nc + 1) * 8),
+		dev_buf(k.tile_cnt, nt * 8),
+		dev_buf(k.scan_tmp, (scan_items / 1024 + 4) * 8),
+		dev_buf(k.pcode, nb + 16),
+		dev_buf(k.pstart, nb * 4),
+		dev_buf(k.pend, nb * 4),
+		dev_buf(k.phz, nb * 8),
+		dev_buf(k.sx, nb * 8),
+		dev_buf(k.sy, nb * 8),
+		dev_buf(k.sn, nb + 16),
+		dev_buf(k.slc, nb),
+		dev_buf(k.sseq, nb * 4),
+		dev_buf(k.scnt, nb * 4)};
+	for (const chaindp::DevBuf &b : bufs) ctx->pool.release(b.slot);
+	ctx->sk_cap_bases = ctx->sk_cap_chunks = ctx->sk_cap_seqs = -1;
+	const hipError_t e = (hipError_t)ctx->pool.alloc_group(bufs, 20);
 	if (e != hipSuccess) {
 		(void)hipGetLastError();
-		for (void *b : ctx->sk_allocs) if (b) (void)hipFree(b);
-		ctx->sk_allocs.clear();
-		ctx->sk = {};
 		ctx->err = std::string("sketch buffers for ") + std::to_string((long long)n_bases) + " bases: " + hipGetErrorString(e);
 		return CHAINDP_ERR_CAPACITY;
 	}
-	k.seq = d_seq; k.seq_off = d_seq_off; k.chunk_seq = d_chunk_seq; k.seq_chunk0 = d_seq_chunk0; k.read_seq0 = d_read_seq0; k.seq_ybase = d_ybase;
 	ctx->sk_cap_bases = (int64_t)nb - 16; ctx->sk_cap_chunks = (int64_t)nc; ctx->sk_cap_seqs = (int64_t)nq;
 	return CHAINDP_OK;
 }
@@ -1303,8 +1273,8 @@ static int sketch_impl(chaindp_ctx *ctx, int w, int k, int is_hpc, int64_t n_seq
 	if (!ctx->seed_ready && (rc = seed_reserve(ctx, 0)) != CHAINDP_OK) return rc;
 	// A sketch starts a new batch.  Its minimizers go to the buffers of the seed collection, which may have to grow (and with them
 	// the mini_pos[] an earlier batch left), so that batch is dropped here: its downloads are refused or return nothing from now on.
-	ctx->n_reads = 0; ctx->total = 0; ctx->n_seeds = 0; ctx->n_mini_pos = 0; ctx->ran = false; ctx->compact_ready = false; ctx->singles_pending = false;
-	ctx->bot_n_reads = -1; ctx->mp_resident = false; ctx->regs_resident = false; ctx->sk_valid = false;
+	begin_batch(ctx, 0, 0);
+	ctx->n_seeds = 0; ctx->n_mini_pos = 0; ctx->singles_pending = false; ctx->regs_resident = false; ctx->sk_valid = false;
 	hipStream_t st = ctx->stream;
 	chaindp::SketchArgs a = ctx->sk;
 	a.w = w; a.k = k; a.is_hpc = is_hpc != 0; a.n_seqs = n_seqs; a.n_chunks = n_chunks;
@@ -1449,15 +1419,6 @@ extern "C" chaindp_pipe_t *chaindp_pipe_create(int device, int depth, int64_t ma
 	return pipe;
 }
 
-#define PIPE_TRY(pipe, call)                                                                       \
-	do {                                                                                           \
-		hipError_t e_ = (call);                                                                    \
-		if (e_ != hipSuccess) {                                                                    \
-			(pipe)->err = std::string(#call) + ": " + hipGetErrorString(e_);                       \
-			return CHAINDP_ERR_HIP;                                                                \
-		}                                                                                          \
-	} while (0)
-
 extern "C" int chaindp_pipe_submit(chaindp_pipe_t *pipe, const chaindp_params_t *par, int64_t n_reads, const int64_t *off,
                                    const chaindp_anchor_t *a, const int32_t *n_segs_per_read, int64_t tag)
 {
@@ -1471,22 +1432,21 @@ extern "C" int chaindp_pipe_submit(chaindp_pipe_t *pipe, const chaindp_params_t 
 	const int64_t total = n_reads > 0 ? off[n_reads] : 0;
 	if (total < 0 || (total > 0 && !a)) { pipe->err = "bad anchors"; return CHAINDP_ERR_ARG; }
 	if (n_reads > ctx->cap_reads || total > ctx->cap_anchors) { pipe->err = "batch exceeds the capacity the pipe was created with"; return CHAINDP_ERR_CAPACITY; }
-	PIPE_TRY(pipe, hipSetDevice(pipe->device));
+	HIP_TRY(pipe, hipSetDevice(pipe->device));
 	hipStream_t st = ctx->stream;
 	// upload on the pipe's upload stream (the slot's previous batch has been waited for, so its buffers are free); the
 	// slot's own stream takes over for the kernels once the upload is in
-	PIPE_TRY(pipe, hipMemcpyAsync(ctx->d_off, off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, pipe->s_up));
-	if (total) PIPE_TRY(pipe, hipMemcpyAsync(ctx->d_a, a, (size_t)total * 16, hipMemcpyHostToDevice, pipe->s_up));
-	ctx->has_n_segs = n_segs_per_read != nullptr;
-	if (n_segs_per_read && n_reads) PIPE_TRY(pipe, hipMemcpyAsync(ctx->d_n_segs, n_segs_per_read, (size_t)n_reads * 4, hipMemcpyHostToDevice, pipe->s_up));
-	PIPE_TRY(pipe, hipEventRecord(sl.up, pipe->s_up));
-	PIPE_TRY(pipe, hipStreamWaitEvent(st, sl.up, 0));
-	ctx->n_reads = n_reads; ctx->total = total; ctx->ran = false; ctx->bot_n_reads = -1; ctx->mp_resident = false;
+	HIP_TRY(pipe, hipMemcpyAsync(ctx->d_off, off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, pipe->s_up));
+	if (total) HIP_TRY(pipe, hipMemcpyAsync(ctx->d_a, a, (size_t)total * 16, hipMemcpyHostToDevice, pipe->s_up));
+	HIP_TRY(pipe, stage_n_segs(ctx, n_segs_per_read, n_reads, pipe->s_up));
+	HIP_TRY(pipe, hipEventRecord(sl.up, pipe->s_up));
+	HIP_TRY(pipe, hipStreamWaitEvent(st, sl.up, 0));
+	begin_batch(ctx, n_reads, total);
 	rc = chaindp_run_full(ctx, par);
 	if (rc) { pipe->err = ctx->err; return rc; }
-	PIPE_TRY(pipe, hipMemcpyAsync(sl.h_seeds_off, ctx->d_seeds_off, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
-	PIPE_TRY(pipe, hipMemcpyAsync(sl.h_n_seeds, ctx->cmp.n_seeds, 8, hipMemcpyDeviceToHost, st));
-	PIPE_TRY(pipe, hipEventRecord(sl.done, st));
+	HIP_TRY(pipe, hipMemcpyAsync(sl.h_seeds_off, ctx->d_seeds_off, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(pipe, hipMemcpyAsync(sl.h_n_seeds, ctx->cmp.n_seeds, 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(pipe, hipEventRecord(sl.done, st));
 	sl.tag = tag; sl.n_reads = n_reads; sl.total = total; sl.state = 1;
 	pipe->head = (pipe->head + 1) % pipe->depth;
 	++pipe->inflight;
@@ -1498,17 +1458,17 @@ extern "C" int chaindp_pipe_wait(chaindp_pipe_t *pipe, chaindp_pipe_result_t *re
 	if (!pipe || !res) return CHAINDP_ERR_ARG;
 	PipeSlot &sl = pipe->slots[(size_t)pipe->tail];
 	if (pipe->inflight == 0 || sl.state != 1) { pipe->err = sl.state == 2 ? "release the batch waited for first" : "nothing in flight"; return CHAINDP_ERR_BUSY; }
-	PIPE_TRY(pipe, hipSetDevice(pipe->device));
-	PIPE_TRY(pipe, hipEventSynchronize(sl.done));
+	HIP_TRY(pipe, hipSetDevice(pipe->device));
+	HIP_TRY(pipe, hipEventSynchronize(sl.done));
 	// the record count is known now: download exactly the batch's new_seed[] (the other slots' uploads and kernels go on)
 	const int64_t m = sl.total > 0 && sl.n_reads > 0 ? (int64_t)(uint32_t)*sl.h_n_seeds : 0;
 	sl.ctx->n_seeds = m;
 	if (m > 0) {
 		// a few workgroups are enough to fill the link and leave the shader array to the other slots' kernels
 		static const int copy_blocks = getenv("CHAINDP_PIPE_COPY_BLOCKS") ? atoi(getenv("CHAINDP_PIPE_COPY_BLOCKS")) : 64;
-		if (copy_blocks > 0) PIPE_TRY(pipe, chaindp::launch_copy_out(pipe->s_down, sl.h_seeds, sl.ctx->d_seeds, (size_t)m * sizeof(chaindp_seed_t), copy_blocks));
-		else PIPE_TRY(pipe, hipMemcpyAsync(sl.h_seeds, sl.ctx->d_seeds, (size_t)m * sizeof(chaindp_seed_t), hipMemcpyDeviceToHost, pipe->s_down));
-		PIPE_TRY(pipe, hipStreamSynchronize(pipe->s_down));
+		if (copy_blocks > 0) HIP_TRY(pipe, chaindp::launch_copy_out(pipe->s_down, sl.h_seeds, sl.ctx->d_seeds, (size_t)m * sizeof(chaindp_seed_t), copy_blocks));
+		else HIP_TRY(pipe, hipMemcpyAsync(sl.h_seeds, sl.ctx->d_seeds, (size_t)m * sizeof(chaindp_seed_t), hipMemcpyDeviceToHost, pipe->s_down));
+		HIP_TRY(pipe, hipStreamSynchronize(pipe->s_down));
 	}
 	if (sl.n_reads == 0) sl.h_seeds_off[0] = 0;
 	res->tag = sl.tag; res->n_reads = sl.n_reads; res->n_anchors = sl.total; res->n_seeds = m;
@@ -1560,16 +1520,35 @@ extern "C" int64_t chaindp_post_logf_patches(uint32_t *k, float *v, int64_t cap)
 
 static int post_logf_upload(chaindp_ctx *ctx)
 {
-	if (ctx->n_logf >= 0) return CHAINDP_OK;
+	if (ctx->logf_ready) return CHAINDP_OK;
 	build_logf_patches();
-	const size_t n = g_logf_k.size();
-	HIP_TRY(ctx, bot_alloc(ctx, ctx->d_logf_k, (n ? n : 1) * 4));
-	HIP_TRY(ctx, bot_alloc(ctx, ctx->d_logf_v, (n ? n : 1) * 4));
-	if (n) {
-		HIP_TRY(ctx, hipMemcpy(ctx->d_logf_k, g_logf_k.data(), n * 4, hipMemcpyHostToDevice));
-		HIP_TRY(ctx, hipMemcpy(ctx->d_logf_v, g_logf_v.data(), n * 4, hipMemcpyHostToDevice));
+	const size_t n = g_logf_k.size(), m = ctx->pool.mark();
+	hipError_t e = (hipError_t)ctx->pool.alloc_group({dev_buf(ctx->d_logf_k, (n ? n : 1) * 4), dev_buf(ctx->d_logf_v, (n ? n : 1) * 4)});
+	if (e == hipSuccess && n) e = hipMemcpy(ctx->d_logf_k, g_logf_k.data(), n * 4, hipMemcpyHostToDevice);
+	if (e == hipSuccess && n) e = hipMemcpy(ctx->d_logf_v, g_logf_v.data(), n * 4, hipMemcpyHostToDevice);
+	if (e != hipSuccess) {
+		ctx->pool.rollback(m);
+		ctx->err = std::string("logf patch tables: ") + hipGetErrorString(e);
+		return CHAINDP_ERR_HIP;
 	}
-	ctx->n_logf = (int)n;
+	ctx->n_logf = (int)n; ctx->logf_ready = true;
+	return CHAINDP_OK;
+}
+
+// everything chaindp_chain_post and chaindp_frag_post share on the device, for a batch of n_c chains with n_b chain anchors
+static int post_reserve(chaindp_ctx *ctx, int64_t n_c, int64_t n_b)
+{
+	int rc = regs_per_read_buffers(ctx);
+	if (rc) return rc;
+	if ((rc = post_logf_upload(ctx)) != CHAINDP_OK) return rc;
+	const size_t RB = (size_t)ctx->cap_reads + 2;
+	rc = first_use(ctx, ctx->post_ready, "chain_post", {dev_buf(ctx->d_post_off, RB * 8), dev_buf(ctx->d_post_tile, (RB / 1024 + 2) * 8),
+	                                                    dev_buf(ctx->d_post_qlen, RB * 4), dev_buf(ctx->d_post_rep, RB * 4), dev_buf(ctx->d_post_err, 4)});
+	if (rc) return rc;
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_post_stage, ctx->post_stage_cap, (size_t)n_c * sizeof(chaindp_reg_t)));
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_post_out, ctx->post_out_cap, (size_t)n_c * sizeof(chaindp_reg_t)));
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_post_sq, ctx->post_sq_cap, (size_t)(n_b > 0 ? n_b : 1) * 16));
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_post_scratch, ctx->post_scratch_cap, (size_t)n_c * POST_SCRATCH_INTS * 4));
 	return CHAINDP_OK;
 }
 
@@ -1635,29 +1614,14 @@ extern "C" int chaindp_chain_post(chaindp_ctx_t *ctx, const chaindp_post_opt_t *
 		HIP_TRY(ctx, hipStreamSynchronize(st));
 		for (int32_t v : ns) if (v > 1) { ctx->err = "chaindp_chain_post takes single-segment reads only (n_segs > 1)"; return CHAINDP_ERR_ARG; }
 	}
-	if (R == 0) { regs_off[0] = 0; if (a_off) a_off[0] = 0; return CHAINDP_OK; }
-	if (n_c == 0) {
-		for (int64_t r = 0; r <= R; ++r) regs_off[r] = 0;
-		if (a_off) for (int64_t r = 0; r <= R; ++r) a_off[r] = 0;
+	if (R == 0 || n_c == 0) {
+		for (int64_t r = 0; r <= R; ++r) { regs_off[r] = 0; if (a_off) a_off[r] = 0; }
 		return CHAINDP_OK;
 	}
-	const bool mp_given = mini_pos != nullptr || mini_pos_off != nullptr;
-	if (do_err && !mp_given && (!ctx->mp_resident || !ctx->d_mp_off)) { ctx->err = "no resident mini_pos: pass the arrays, or collect the seeds with chaindp_collect_seeds"; return CHAINDP_ERR_ARG; }
-	if (do_err && mp_given && !mini_pos_off) { ctx->err = "mini_pos without offsets"; return CHAINDP_ERR_ARG; }
-	if (do_mapq && !rep_len && !ctx->mp_resident) { ctx->err = "no resident rep_len: pass it, or collect the seeds with chaindp_collect_seeds"; return CHAINDP_ERR_ARG; }
-	int rc = regs_per_read_buffers(ctx);
+	int rc = do_err ? mini_pos_check(ctx, mini_pos_off, mini_pos) : CHAINDP_OK;
 	if (rc) return rc;
-	if ((rc = post_logf_upload(ctx)) != CHAINDP_OK) return rc;
-	const size_t RB = (size_t)ctx->cap_reads + 2;
-	if (!ctx->d_post_off) {
-		HIP_TRY(ctx, bot_alloc(ctx, ctx->d_post_off, RB * 8)); HIP_TRY(ctx, bot_alloc(ctx, ctx->d_post_tile, (RB / 1024 + 2) * 8));
-		HIP_TRY(ctx, bot_alloc(ctx, ctx->d_post_qlen, RB * 4)); HIP_TRY(ctx, bot_alloc(ctx, ctx->d_post_rep, RB * 4));
-		HIP_TRY(ctx, bot_alloc(ctx, ctx->d_post_err, 4));
-	}
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_post_stage, ctx->post_stage_cap, (size_t)n_c * sizeof(chaindp_reg_t)));
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_post_out, ctx->post_out_cap, (size_t)n_c * sizeof(chaindp_reg_t)));
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_post_sq, ctx->post_sq_cap, (size_t)(n_b > 0 ? n_b : 1) * 16));
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_post_scratch, ctx->post_scratch_cap, (size_t)n_c * POST_SCRATCH_INTS * 4));
+	if (do_mapq && !rep_len && !ctx->mp_resident) { ctx->err = "no resident rep_len: pass it, or collect the seeds with chaindp_collect_seeds"; return CHAINDP_ERR_ARG; }
+	if ((rc = post_reserve(ctx, n_c, n_b)) != CHAINDP_OK) return rc;
 	const int32_t *d_qlen = ctx->d_rqlen;
 	if (qlen) { HIP_TRY(ctx, hipMemcpyAsync(ctx->d_post_qlen, qlen, (size_t)R * 4, hipMemcpyHostToDevice, st)); d_qlen = ctx->d_post_qlen; }
 	const int32_t *d_rep = ctx->d_rep_len;
@@ -1673,18 +1637,9 @@ extern "C" int chaindp_chain_post(chaindp_ctx_t *ctx, const chaindp_post_opt_t *
 	const int64_t n_out = regs_off[R];
 	if (n_out > regs_cap) { ctx->err = "more hits than regs has room for (regs_off is valid)"; return CHAINDP_ERR_CAPACITY; }
 	if (do_err && n_out > 0) {
-		const int64_t *d_mpo = ctx->d_mp_off;
-		const unsigned long long *d_mp = ctx->d_mini_pos;
-		if (mp_given) {
-			const int64_t n_mp = mini_pos_off[R];
-			if (n_mp < 0 || (n_mp > 0 && !mini_pos)) { ctx->err = "mini_pos announced but absent"; return CHAINDP_ERR_ARG; }
-			HIP_TRY(ctx, regs_grow(ctx, ctx->d_mp_up, ctx->mp_up_cap, (size_t)(n_mp > 0 ? n_mp : 1) * 8));
-			HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mp_off_up, mini_pos_off, (size_t)(R + 1) * 8, hipMemcpyHostToDevice, st));
-			if (n_mp > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mp_up, mini_pos, (size_t)n_mp * 8, hipMemcpyHostToDevice, st));
-			d_mpo = ctx->d_mp_off_up; d_mp = (const unsigned long long*)ctx->d_mp_up;
-		}
-		HIP_TRY(ctx, regs_grow(ctx, ctx->d_ref_len, ctx->ref_len_cap, (size_t)(n_ref > 0 ? n_ref : 1) * 4));
-		if (n_ref > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ref_len, ref_len, (size_t)n_ref * 4, hipMemcpyHostToDevice, st));
+		const int64_t *d_mpo = nullptr;
+		const unsigned long long *d_mp = nullptr;
+		if ((rc = stage_mini_pos(ctx, R, mini_pos_off, mini_pos, ref_len, n_ref, d_mpo, d_mp)) != CHAINDP_OK) return rc;
 		// k_regs_div over the packed output, with the anchors as chain_post left them (mm_est_err at map.c:872)
 		HIP_TRY(ctx, chaindp::launch_est_err(st, R, n_out, (const int64_t*)ctx->d_post_off, ctx->bot.b_off, ctx->d_post_sq, d_qlen,
 		                                     (const int32_t*)ctx->d_ref_len, n_ref, d_mpo, d_mp, ctx->d_sum_k, ctx->d_post_out, nullptr));
@@ -1712,14 +1667,9 @@ extern "C" int chaindp_map_reads(chaindp_ctx_t *ctx, const chaindp_index_t *ix, 
 	if (rc) return rc;
 	if (!opt || !regs_off || regs_cap < 0 || (regs_cap > 0 && !regs) || (n_reads > 0 && !hash)) { ctx->err = "NULL output, hash or opt"; return CHAINDP_ERR_ARG; }
 	if (par->n_segs > 1) { ctx->err = "chaindp_map_reads takes single-segment reads only (n_segs > 1)"; return CHAINDP_ERR_ARG; }
-	if (!mini && !mini_off && !qlen && ctx->sk_valid && n_reads == ctx->sk_n_reads) qlen = ctx->sk_qlen.data();   // the resident sketch's (checked below)
 	// the stages of chaindp_map_batch, with the hits left in HBM, then chain_post on them
-	if ((rc = collect_seeds_impl(ctx, ix, flag, max_occ, n_reads, mini_off, mini, nullptr, bid, qlen, nullptr, nullptr, rep_len, nullptr)) != CHAINDP_OK) return rc;
-	if (n_anchors) *n_anchors = ctx->total;
-	if ((rc = chaindp_run_full(ctx, par)) != CHAINDP_OK) return rc;
-	std::vector<int64_t> c_off((size_t)(n_reads > 0 ? n_reads + 1 : 1)), b_off(c_off.size());
-	if ((rc = chaindp_backtrack(ctx, par, min_cnt, c_off.data(), nullptr, b_off.data(), nullptr)) != CHAINDP_OK) return rc;
-	if ((rc = gen_regs_impl(ctx, hash, qlen, nullptr, false)) != CHAINDP_OK) return rc;
+	rc = map_prefix(ctx, ix, flag, max_occ, par, min_cnt, n_reads, mini_off, mini, bid, qlen, nullptr, hash, rep_len, n_anchors, nullptr, nullptr, 0);
+	if (rc) return rc;
 	return chaindp_chain_post(ctx, opt, nullptr, nullptr, ref_len, n_ref, nullptr, nullptr, regs_off, regs, regs_cap, nullptr, nullptr);
 }
 
@@ -1808,27 +1758,15 @@ static int frag_post_impl(chaindp_ctx *ctx, const chaindp_post_opt_t *opt, int64
 		}
 	}
 	const bool do_err = !opt->is_sr && any_single;               // mm_seg_gen rebuilds the records of the other reads: div = -1 there
-	const bool mp_given = mini_pos != nullptr || mini_pos_off != nullptr;
-	if (do_err && !mp_given && (!ctx->mp_resident || !ctx->d_mp_off)) { ctx->err = "no resident mini_pos: pass the arrays, or collect the seeds with chaindp_collect_seeds"; return CHAINDP_ERR_ARG; }
-	if (do_err && mp_given && !mini_pos_off) { ctx->err = "mini_pos without offsets"; return CHAINDP_ERR_ARG; }
-	if (do_mapq && !rep_len && !ctx->mp_resident) { ctx->err = "no resident rep_len: pass it, or collect the seeds with chaindp_collect_seeds"; return CHAINDP_ERR_ARG; }
-	int rc = regs_per_read_buffers(ctx);
+	int rc = do_err ? mini_pos_check(ctx, mini_pos_off, mini_pos) : CHAINDP_OK;
 	if (rc) return rc;
-	if ((rc = post_logf_upload(ctx)) != CHAINDP_OK) return rc;
-	const size_t RB = (size_t)ctx->cap_reads + 2;
-	if (!ctx->d_post_off) {
-		HIP_TRY(ctx, bot_alloc(ctx, ctx->d_post_off, RB * 8)); HIP_TRY(ctx, bot_alloc(ctx, ctx->d_post_tile, (RB / 1024 + 2) * 8));
-		HIP_TRY(ctx, bot_alloc(ctx, ctx->d_post_qlen, RB * 4)); HIP_TRY(ctx, bot_alloc(ctx, ctx->d_post_rep, RB * 4));
-		HIP_TRY(ctx, bot_alloc(ctx, ctx->d_post_err, 4));
-	}
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_post_stage, ctx->post_stage_cap, (size_t)n_c * sizeof(chaindp_reg_t)));
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_post_out, ctx->post_out_cap, (size_t)n_c * sizeof(chaindp_reg_t)));
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_post_sq, ctx->post_sq_cap, (size_t)(n_b > 0 ? n_b : 1) * 16));
+	if (do_mapq && !rep_len && !ctx->mp_resident) { ctx->err = "no resident rep_len: pass it, or collect the seeds with chaindp_collect_seeds"; return CHAINDP_ERR_ARG; }
+	if ((rc = post_reserve(ctx, n_c, n_b)) != CHAINDP_OK) return rc;
 	// per sequence: read_seq0[R + 1] | seq_len | seq_read | seq_rep | seq_hash; counts -> offsets: 3 x (S + 1), then the scans' scratch
 	const size_t SB = (size_t)S + 2, tile_items = SB / 1024 + 2;
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_frag_seq, ctx->frag_seq_cap, ((size_t)R + 2 + 4 * SB) * 4));
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_frag_cnt, ctx->frag_cnt_cap, (3 * SB + tile_items) * 8));
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_frag_a, ctx->frag_a_cap, (size_t)(n_b > 0 ? n_b : 1) * 16));
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_frag_seq, ctx->frag_seq_cap, ((size_t)R + 2 + 4 * SB) * 4));
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_frag_cnt, ctx->frag_cnt_cap, (3 * SB + tile_items) * 8));
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_frag_a, ctx->frag_a_cap, (size_t)(n_b > 0 ? n_b : 1) * 16));
 	int32_t *d_read_seq0 = (int32_t*)ctx->d_frag_seq, *d_seq_len = d_read_seq0 + R + 2, *d_seq_read = d_seq_len + SB, *d_seq_rep = d_seq_read + SB;
 	uint32_t *d_seq_hash = (uint32_t*)(d_seq_rep + SB);
 	unsigned long long *d_g = (unsigned long long*)ctx->d_frag_cnt, *d_o = d_g + SB, *d_a = d_o + SB, *d_tile = d_a + SB;
@@ -1839,8 +1777,7 @@ static int frag_post_impl(chaindp_ctx *ctx, const chaindp_post_opt_t *opt, int64
 	HIP_TRY(ctx, hipMemsetAsync(ctx->d_post_err, 0, 4, st));
 	const chaindp::PostOpt po = to_post_opt(opt);
 	// chain_post per read and the first half of mm_seg_gen.  The global scratch of what exceeds the LDS cap is sized for the fragments'
-	// hits here and grown below for the segments' hits, once their count is known.
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_post_scratch, ctx->post_scratch_cap, (size_t)n_c * POST_SCRATCH_INTS * 4));
+	// hits at this point and grown below for the segments' hits, once their count is known.
 	HIP_TRY(ctx, chaindp::launch_frag_read(st, R, ctx->bot.chains_off, ctx->bot.b_off, ctx->bot.b_out, ctx->d_regs, ctx->d_rqlen, d_read_seq0, d_seq_len, po,
 	                                       ctx->ran_par.max_dist_x, ctx->frag_lds_cap, (int32_t*)ctx->d_post_scratch, ctx->d_post_stage, ctx->d_post_sq,
 	                                       ctx->d_post_off, d_g, d_o, d_a));
@@ -1860,29 +1797,20 @@ static int frag_post_impl(chaindp_ctx *ctx, const chaindp_post_opt_t *opt, int64
 	if (n_out > regs_cap) { ctx->err = "more hits than regs has room for (seg_regs_off is valid)"; return CHAINDP_ERR_CAPACITY; }
 	HIP_TRY(ctx, chaindp::launch_post_scatter(st, R, ctx->bot.chains_off, ctx->d_post_off, ctx->d_post_stage, ctx->d_post_out));
 	if (do_err && n_post > 0) {
-		const int64_t *d_mpo = ctx->d_mp_off;
-		const unsigned long long *d_mp = ctx->d_mini_pos;
-		if (mp_given) {
-			const int64_t n_mp = mini_pos_off[R];
-			if (n_mp < 0 || (n_mp > 0 && !mini_pos)) { ctx->err = "mini_pos announced but absent"; return CHAINDP_ERR_ARG; }
-			HIP_TRY(ctx, regs_grow(ctx, ctx->d_mp_up, ctx->mp_up_cap, (size_t)(n_mp > 0 ? n_mp : 1) * 8));
-			HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mp_off_up, mini_pos_off, (size_t)(R + 1) * 8, hipMemcpyHostToDevice, st));
-			if (n_mp > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mp_up, mini_pos, (size_t)n_mp * 8, hipMemcpyHostToDevice, st));
-			d_mpo = ctx->d_mp_off_up; d_mp = (const unsigned long long*)ctx->d_mp_up;
-		}
-		HIP_TRY(ctx, regs_grow(ctx, ctx->d_ref_len, ctx->ref_len_cap, (size_t)(n_ref > 0 ? n_ref : 1) * 4));
-		if (n_ref > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ref_len, ref_len, (size_t)n_ref * 4, hipMemcpyHostToDevice, st));
+		const int64_t *d_mpo = nullptr;
+		const unsigned long long *d_mp = nullptr;
+		if ((rc = stage_mini_pos(ctx, R, mini_pos_off, mini_pos, ref_len, n_ref, d_mpo, d_mp)) != CHAINDP_OK) return rc;
 		// mm_est_err (map.c:872) on the packed hits of every read; only the one-segment reads keep theirs
 		HIP_TRY(ctx, chaindp::launch_est_err(st, R, n_post, (const int64_t*)ctx->d_post_off, ctx->bot.b_off, ctx->d_post_sq, ctx->d_rqlen,
 		                                     (const int32_t*)ctx->d_ref_len, n_ref, d_mpo, d_mp, ctx->d_sum_k, ctx->d_post_out, nullptr));
 	}
 	const size_t ng1 = (size_t)(n_g > 0 ? n_g : 1);
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_frag_u, ctx->frag_u_cap, ng1 * 8));
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_frag_stage, ctx->frag_stage_cap, ng1 * sizeof(chaindp_reg_t)));
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_frag_z, ctx->frag_z_cap, ng1 * 16));
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_frag_stacks, ctx->frag_stacks_cap, (ng1 / 64 + 2 * (size_t)S + 4) * 12));
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_frag_out, ctx->frag_out_cap, (size_t)(n_out > 0 ? n_out : 1) * sizeof(chaindp_reg_t)));
-	HIP_TRY(ctx, regs_grow(ctx, ctx->d_post_scratch, ctx->post_scratch_cap, ng1 * POST_SCRATCH_INTS * 4));
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_frag_u, ctx->frag_u_cap, ng1 * 8));
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_frag_stage, ctx->frag_stage_cap, ng1 * sizeof(chaindp_reg_t)));
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_frag_z, ctx->frag_z_cap, ng1 * 16));
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_frag_stacks, ctx->frag_stacks_cap, (ng1 / 64 + 2 * (size_t)S + 4) * 12));
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_frag_out, ctx->frag_out_cap, (size_t)(n_out > 0 ? n_out : 1) * sizeof(chaindp_reg_t)));
+	HIP_TRY(ctx, dev_grow(ctx, ctx->d_post_scratch, ctx->post_scratch_cap, ng1 * POST_SCRATCH_INTS * 4));
 	HIP_TRY(ctx, chaindp::launch_frag_split(st, R, ctx->d_post_off, ctx->d_post_out, ctx->bot.b_off, ctx->d_post_sq, d_read_seq0, d_seq_len, ctx->d_rhash,
 	                                        do_mapq ? d_rep : nullptr, d_g, d_o, d_a, (unsigned long long*)ctx->d_frag_u, ctx->d_frag_a, ctx->d_frag_out,
 	                                        d_seq_hash, d_seq_rep, d_seq_read));
@@ -1925,14 +1853,9 @@ static int map_frags_impl(chaindp_ctx *ctx, const chaindp_index_t *ix, int flag,
 	if (!opt || !seg_regs_off || regs_cap < 0 || (regs_cap > 0 && !regs) || (n_reads > 0 && (!hash || !n_segs_per_read))) {
 		ctx->err = "NULL output, hash, n_segs_per_read or opt"; return CHAINDP_ERR_ARG;
 	}
-	if (!mini && !mini_off && !qlen && ctx->sk_valid && n_reads == ctx->sk_n_reads) qlen = ctx->sk_qlen.data();   // the resident sketch's (checked below)
 	// the stages of chaindp_map_batch with the reads' segment counts, the hits left in HBM, then the fragment post steps on them
-	if ((rc = collect_seeds_impl(ctx, ix, flag, max_occ, n_reads, mini_off, mini, nullptr, bid, qlen, n_segs_per_read, nullptr, rep_len, nullptr)) != CHAINDP_OK) return rc;
-	if (n_anchors) *n_anchors = ctx->total;
-	if ((rc = chaindp_run_full(ctx, par)) != CHAINDP_OK) return rc;
-	std::vector<int64_t> c_off((size_t)(n_reads > 0 ? n_reads + 1 : 1)), b_off(c_off.size());
-	if ((rc = chaindp_backtrack(ctx, par, min_cnt, c_off.data(), nullptr, b_off.data(), nullptr)) != CHAINDP_OK) return rc;
-	if ((rc = gen_regs_impl(ctx, hash, qlen, nullptr, false)) != CHAINDP_OK) return rc;
+	rc = map_prefix(ctx, ix, flag, max_occ, par, min_cnt, n_reads, mini_off, mini, bid, qlen, n_segs_per_read, hash, rep_len, n_anchors, nullptr, nullptr, 0);
+	if (rc) return rc;
 	return frag_post_impl(ctx, opt, n_seqs, n_segs_per_read, seg_len, nullptr, ref_len, n_ref, nullptr, nullptr, seg_regs_off, regs, regs_cap, nullptr, nullptr,
 	                      pe_ori, qlen);
 }
