@@ -16,7 +16,7 @@ struct Params {
 struct Unit {
 	int64_t start;   // global anchor index
 	int32_t read;
-	int32_t len;     // upper bound of its length (next unit's start or end of the read)
+	int32_t len;     // its length: up to the next start of a unit or a singleton, or the end of the read (exact: k_emit_units)
 };
 
 // What k_chain_twin needs of a unit besides its record, so that picking a unit up costs it no trips to sumq[] / off[] / the table:

@@ -277,7 +277,7 @@ __device__ __forceinline__ int unit_class(int32_t len)
 }
 
 __global__ __launch_bounds__(256) void k_emit_units(int64_t n_reads, int64_t n_words, const int64_t *__restrict__ off,
-                                                    const uint64_t *__restrict__ start_mask,
+                                                    const uint64_t *__restrict__ start_mask, const uint64_t *__restrict__ single_mask,
                                                     const unsigned long long *__restrict__ block_base, Unit *__restrict__ units,
                                                     unsigned int *__restrict__ hist, const int2 *__restrict__ block_reads)
 {
@@ -291,20 +291,25 @@ __global__ __launch_bounds__(256) void k_emit_units(int64_t n_reads, int64_t n_w
 	// the wave: the units in front of it inside its block from a row prefix of popcounts (it was up to fifteen loads), the start
 	// behind its last unit from the next non-empty lane (it was a walk over the following words, a load each); only a word whose
 	// next start lies beyond the wave's 64 still walks.
+	// Which anchors start a unit comes from start_mask; where a unit ENDS comes from start_mask | single_mask: the prepass sets one
+	// of the two (never both) at every anchor that is too far from the one before it or is its read's first, so the next bit of
+	// the union behind a unit's start is the unit's true end, and Unit.len is exact (k_chain_twin relies on it: it takes
+	// min(64, len - tile) anchors per tile and tests no gap).
 	const int lane = threadIdx.x & 63;
 	for (int64_t wb = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) & ~(int64_t)63; wb < n_words; wb += (int64_t)gridDim.x * blockDim.x) {
 		const int64_t w = wb + lane;
 		uint64_t m = w < n_words ? start_mask[w] : 0;
+		const uint64_t um = w < n_words ? m | single_mask[w] : 0;    // every anchor at which a unit in front of it ends
 		const uint32_t cnt = (uint32_t)__builtin_popcountll(m);
 		uint32_t incl = cnt;                                         // units up to this word inside its block
 		incl += (uint32_t)dpp_or_old<DPP_ROW_SHR(1), 0xf>(0, (int)incl);
 		incl += (uint32_t)dpp_or_old<DPP_ROW_SHR(2), 0xf>(0, (int)incl);
 		incl += (uint32_t)dpp_or_old<DPP_ROW_SHR(4), 0xf>(0, (int)incl);
 		incl += (uint32_t)dpp_or_old<DPP_ROW_SHR(8), 0xf>(0, (int)incl);
-		const uint64_t nz = __builtin_amdgcn_ballot_w64(m != 0);
+		const uint64_t nz = __builtin_amdgcn_ballot_w64(um != 0);
 		const uint64_t above = lane < 63 ? nz & (~0ull << (lane + 1)) : 0ull;
-		const int nl = above ? __builtin_ctzll(above) : lane;        // the next lane that has a unit start
-		const int first_there = __shfl(m ? __builtin_ctzll(m) : 0, nl, 64);
+		const int nl = above ? __builtin_ctzll(above) : lane;        // the next lane that has a start (of a unit or a singleton)
+		const int first_there = __shfl(um ? __builtin_ctzll(um) : 0, nl, 64);
 		const int64_t next_in_wave = above ? ((wb + nl) << 6) + first_there : -1;
 		if (m) {
 			const int64_t b = w / PRE_WORDS;
@@ -319,13 +324,13 @@ __global__ __launch_bounds__(256) void k_emit_units(int64_t n_reads, int64_t n_w
 				m &= m - 1;
 				const int64_t g = (w << 6) + bit;
 				while (g >= re) re = off[++r + 1];                   // units of one word are in anchor order; reads only move forward
-				// upper bound of the unit: the next unit's start or the end of the read (singletons in between are
-				// not units, so this can overshoot the true end; the DP kernel finds the true end itself)
+				// the unit's end: the next start of a unit or a singleton, or the end of the read
 				int64_t next = -1;
-				if (m) next = (w << 6) + __builtin_ctzll(m);
+				const uint64_t behind = bit < 63 ? um & (~0ull << (bit + 1)) : 0ull;
+				if (behind) next = (w << 6) + __builtin_ctzll(behind);
 				else if (next_in_wave >= 0) next = next_in_wave;
 				else for (int64_t k = wb + 64; k < n_words && (k << 6) < re; ++k) {
-					const uint64_t mm = start_mask[k];
+					const uint64_t mm = start_mask[k] | single_mask[k];
 					if (mm) { next = (k << 6) + __builtin_ctzll(mm); break; }
 				}
 				const int64_t end = next >= 0 && next < re ? next : re;
@@ -453,7 +458,7 @@ hipError_t launch_prepass(hipStream_t st, const Params &par, int64_t n_reads, in
 	                   d_sumq, sc.start_mask, sc.single_mask, sc.emit_mask, sc.block_cnt, sc.block_reads);
 	if ((e = launch_scan_u64(st, blocks, sc.block_cnt, sc.tile_tmp, d_counters)) != hipSuccess) return e;
 	hipLaunchKernelGGL(k_emit_units, dim3((unsigned)((words + 255) / 256 < 2048 ? (words + 255) / 256 : 2048)), dim3(256), 0, st, n_reads, words, d_off,
-	                   sc.start_mask, sc.block_cnt, sc.units_tmp, sc.hist, sc.block_reads);
+	                   sc.start_mask, sc.single_mask, sc.block_cnt, sc.units_tmp, sc.hist, sc.block_reads);
 	hipLaunchKernelGGL(k_unit_bases, dim3(1), dim3(64), 0, st, sc.hist, sc.hist + UNIT_CLASSES, d_unit_aux ? sc.key_range : nullptr);
 	hipLaunchKernelGGL(k_unit_scatter, dim3((unsigned)(blocks < 1024 ? (blocks > 0 ? blocks : 1) : 1024)), dim3(256), 0, st, d_counters, sc.units_tmp,
 	                   sc.hist, sc.hist + UNIT_CLASSES, d_units, par, d_off, d_sumq, d_unit_aux, d_unit_aux ? sc.key_range : nullptr, d_n_segs);

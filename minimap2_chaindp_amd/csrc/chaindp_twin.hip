@@ -155,11 +155,12 @@ __device__ __forceinline__ uint32_t tw_both_halves(uint64_t m)
 	return t;
 }
 
-// per half: bits of m below the half's lowest set bit of b (all of m where b has none)
+// per half: bits of m below the half's lowest set bit of b (all of m where b has none: (b - 1) & ~b is all ones for b = 0).  The
+// halves as scalar words of their own: from "b's high word is not zero" the compiler makes a 64-bit vector compare.
 __device__ __forceinline__ uint64_t tw_below_first(uint64_t m, uint64_t b)
 {
-	const uint32_t blo = (uint32_t)b, bhi = (uint32_t)(b >> 32);
-	const uint32_t klo = blo ? (blo & (0u - blo)) - 1u : 0xffffffffu, khi = bhi ? (bhi & (0u - bhi)) - 1u : 0xffffffffu;
+	const uint32_t blo = TW_UNI((uint32_t)b), bhi = TW_UNI((uint32_t)(b >> 32));
+	const uint32_t klo = (blo - 1u) & ~blo, khi = (bhi - 1u) & ~bhi;
 	return m & ((uint64_t)khi << 32 | klo);
 }
 
@@ -236,7 +237,7 @@ struct TwinArgs {
 struct TwinCold {                     // 40 bytes at ST + 56 h (8-byte aligned: read and written as 64-bit words)
 	int64_t next;                     // next unit of this half (grid-stride over pairs)
 	int64_t base;                     // global index of the unit's first anchor
-	uint64_t x_carry;                 // x of the previous tile's last anchor
+	uint32_t params_ok, spare;        // the launch's parameters are this kernel's (written once, when the kernel starts)
 	int32_t rel0, room, read, tile0;  // unit start relative to its read; anchors the unit may have; its read; current tile's first anchor
 };
 
@@ -332,7 +333,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 		return;
 	}
 	if (blockIdx.x == 0 && lane == 0) *g.route = ONE_LUT ? 2u : 3u;
-	// (whether the parameters are this kernel's at all is asked where a unit is picked up: params_ok in service())
+	// the parameters are this kernel's (else every unit is handed over).  The kernel's 32-bit differences (and the signed window
+	// test) are exact while 129 * (max_dist_x + 1) < 2^31.  Decided here, once, from the kernel arguments, and kept in the halves'
+	// cold state: service() finds it there where it picks a unit up.
+	const bool params_ok = g.lut != nullptr && !g.par.is_cdna && g.par.max_dist_x >= 1 && g.par.max_dist_y >= 0 && g.par.n_segs <= 1 &&
+	                       ((uint64_t)(int64_t)g.par.max_dist_x + 1) * 129ull < (1ull << 31) && g.par.bw + 1 <= (int)TW_LUT_BYTES && g.force_left != 1;
 
 	TwinHot u;
 	u.S = 0; u.m4 = 0; u.pc = L::HAS_XQ ? curbase : 0u; u.pend = u.pc;
@@ -354,7 +359,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 	// register allocation of every instantiation tips into VGPR spills)
 	const uint32_t xcd = blockIdx.x & 7u;
 	const uint64_t end_units = (uint64_t)TW_END_UNITS * 2u * gridDim.x;      // TW_END_UNITS per half
-	const uint32_t U1 = n_units > end_units ? (n_units - (uint32_t)end_units) & ~(8u * TW_QCH - 1u) : 0u;
+	const uint32_t U1 = (end_units >> 32) == 0 && n_units > (uint32_t)end_units ? (n_units - (uint32_t)end_units) & ~(8u * TW_QCH - 1u) : 0u;
 	const uint32_t G1k = U1 / (8u * TW_QCH);                             // grabs of whole chunks per counter
 	auto grab = [&](uint32_t p, uint32_t &nx, uint32_t &ne) {
 		if (p < G1k) { nx = (8u * p + xcd) * TW_QCH; ne = nx + TW_QCH; }
@@ -364,7 +369,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 		uint32_t nx, ne;
 		grab(((blockIdx.x >> 3) << 1) | (uint32_t)h, nx, ne);                            // the half's first grab: dealt statically
 		tw_st64(st_addr, nx, ne); tw_st64(st_addr + 8u, 0u, 0u);                         // TwinCold: next (low word: next unit, high word: end of the chunk), base
-		tw_st64(st_addr + 16u, 0u, 0u); tw_st64(st_addr + 24u, 0u, 0u);                 // x_carry, rel0, room
+		tw_st64(st_addr + 16u, params_ok ? 1u : 0u, 0u); tw_st64(st_addr + 24u, 0u, 0u);   // params_ok, rel0, room
 		tw_st64(st_addr + 32u, 0u, (uint32_t)-TW_TILE);                                 // read, tile0
 		tw_st64(st_addr + TW_CARRY, 0xfffffffcu, 0u); tw_st64(st_addr + TW_CARRY + 8u, 0u, 0u);   // carry, second chunks so far
 		tw_st32(L::KEY + 4u * (uint32_t)h, -1);                                         // no table yet (an avg_qspan is never a NaN)
@@ -412,7 +417,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 			const tw_u32x2 cw0 = tw_ld64(sa), cw1 = tw_ld64(sa + 8u), cw2 = tw_ld64(sa + 16u), cw3 = tw_ld64(sa + 24u), cw4 = tw_ld64(sa + 32u);
 			int64_t c_next = (int64_t)((uint64_t)TW_UNI(cw0.y) << 32 | TW_UNI(cw0.x));
 			int64_t c_base = (int64_t)((uint64_t)TW_UNI(cw1.y) << 32 | TW_UNI(cw1.x));
-			uint64_t c_xcarry = (uint64_t)TW_UNI(cw2.y) << 32 | TW_UNI(cw2.x);
+			const bool params_ok = TW_UNI(cw2.x) != 0;                        // (decided when the kernel started)
 			int c_rel0 = (int)TW_UNI(cw3.x), c_room = (int)TW_UNI(cw3.y), c_read = (int)TW_UNI(cw4.x), c_tile0 = (int)TW_UNI(cw4.y);
 			// anchors of the tile a half holds (the one just scored, or the one taken in this call)
 			auto tile_cnt = [&]() -> int {
@@ -426,38 +431,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 			const int tile_prev = c_tile0, rel0_prev = c_rel0;
 			const int64_t base_prev = c_base;
 			bool live = true;
-			// the parameters are this kernel's (else every unit is handed over).  The kernel's 32-bit differences (and the signed window
-			// test) are exact while 129 * (max_dist_x + 1) < 2^31.  Asked where a unit is picked up, from the kernel arguments.
-			auto params_ok = [&]() -> bool {
-				return kp->lut != nullptr && !kp->par.is_cdna && kp->par.max_dist_x >= 1 && kp->par.max_dist_y >= 0 && kp->par.n_segs <= 1 &&
-				       ((uint64_t)(int64_t)kp->par.max_dist_x + 1) * 129ull < (1ull << 31) && kp->par.bw + 1 <= (int)TW_LUT_BYTES && kp->force_left != 1;
-			};
 			// The half's next unit (PF: and the one after it), in case this call needs them -- the unit ends here, or (PF) with the tile
 			// taken now, and its successor's first tile is then requested a tile ahead: records and UnitAux through the scalar cache,
 			// issued before the work below and read after it.
 			const uint32_t nx0 = (uint32_t)c_next, ne0 = (uint32_t)((uint64_t)c_next >> 32);
 			tw_u32x4 rec0 = {0u, 0u, 0u, 0u}, aux0 = {0u, 0u, 0u, 0u}, rec1 = {0u, 0u, 0u, 0u};
 			const bool rec0_ok = nx0 < ne0 && nx0 < n_units;       // (whenever they are known: a unit can end before its bound says so)
-			const bool rec1_ok = PF && rec0_ok && nx0 + 1u < ne0 && (uint64_t)nx0 + 1u < n_units;
+			const bool rec1_ok = PF && rec0_ok && nx0 + 1u < ne0 && nx0 + 1u < n_units;     // (rec0_ok: nx0 + 1 <= n_units, no wrap)
 			if (rec0_ok) { rec0 = *TW_CONST(tw_u32x4, kp->units + nx0); aux0 = *TW_CONST(tw_u32x4, kp->aux + nx0); }
 			if (rec1_ok) rec1 = *TW_CONST(tw_u32x4, kp->units + nx0 + 1u);
 
-			// takes a tile's anchors (one per lane, raw mm128_t) into the half's LDS: where the unit ends (first gap > max_dist_x,
-			// chain.c:252), XY ring (the anchors as predecessors and as the current anchor), SP.  Returns the anchors the tile holds
-			// (0: the unit ended exactly at its start).
+			// takes a tile's anchors (one per lane, raw mm128_t) into the half's LDS: XY ring (the anchors as predecessors and as the
+			// current anchor), SP.  The unit's length is exact (k_emit_units: the first gap > max_dist_x behind its start, chain.c:252,
+			// or its read's end), so no gap is tested here.  Returns the anchors the tile holds (0: there are none left).
 			auto take_tile = [&](const uint64_t an_x, const uint64_t an_y) -> int {
 				const int i_lane = c_tile0 + lane;
-				const bool have = i_lane < c_room;
-				uint64_t xp;
-				{
-					uint32_t lo = (uint32_t)wave_shift_up1((int)(uint32_t)an_x, 0), hi = (uint32_t)wave_shift_up1((int)(uint32_t)(an_x >> 32), 0);
-					if (lane == 0) { lo = (uint32_t)c_xcarry; hi = (uint32_t)(c_xcarry >> 32); }
-					xp = (uint64_t)hi << 32 | lo;
-				}
-				const bool stop = !have || (i_lane > 0 && an_x - xp > (uint64_t)(int64_t)kp->par.max_dist_x);
-				const uint64_t stop_m = __builtin_amdgcn_ballot_w64(stop);
-				const int cnt = stop_m ? __builtin_ctzll(stop_m) : TW_TILE;
-				c_xcarry = readlane_u64(an_x, 63);
+				const int cnt = c_room - c_tile0 < TW_TILE ? c_room - c_tile0 : TW_TILE;
 				if constexpr (L::HAS_XQ) { u.pc = TW_SEL(hm, curb, u.pc); u.pend = TW_SEL(hm, curb + ((uint32_t)cnt << 3), u.pend); }
 				else u.pend = TW_SEL(hm, mkb + ((uint32_t)(c_tile0 + cnt - 1) << 2), u.pend);
 				if (cnt == 0) return 0;
@@ -504,7 +493,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 				uint64_t nt_x = 0, nt_y = 0;
 				if constexpr (PF) { nt_x = hs ? nx1_x : nx0_x; nt_y = hs ? nx1_y : nx0_y; }
 				else if (c_tile0 + lane < c_room) { const ulonglong2 t = TW_AT(const ulonglong2, kp->a + (c_base + c_tile0), tw_here(ln << 4)); nt_x = t.x; nt_y = t.y; }
-				if (take_tile(nt_x, nt_y) == 0) goes_on = false;     // (0: the unit ended exactly on the boundary)
+				// (never 0: the test above has seen the anchors.  The test stays: without it the compiler reshapes the loop below so
+				// that its flags merge where an `if (lane == 0)` joins, takes them for per-lane values and moves the service's masks
+				// into vector registers -- 64 VGPRs and scratch in every instantiation)
+				if (take_tile(nt_x, nt_y) == 0) goes_on = false;
 			}
 			TW_STAMP_B(if (g.stamp) st_take += (unsigned int)(TW_NOW() - th0);)
 			// ---- flush the finished tile
@@ -606,7 +598,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 				c_next = (int64_t)((uint64_t)ne << 32 | (nx + 1u));
 				Unit un;
 				un.start = (int64_t)((uint64_t)rec0.y << 32 | rec0.x); un.read = (int32_t)rec0.z; un.len = (int32_t)rec0.w;
-				if (!params_ok() || (aux0.z & 1u) || (ONE_LUT && cur_key_now != 0xffffffffu && aux0.y != cur_key_now)) {
+				if (!params_ok || (aux0.z & 1u) || (ONE_LUT && cur_key_now != 0xffffffffu && aux0.y != cur_key_now)) {
 					// not for this kernel: hand the unit over (the key test, one table per wave, cannot fail: key_range)
 					if (lane == 0) kp->left[atomicAdd(kp->left_cnt, 1u)] = un;
 					continue;
@@ -638,7 +630,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 				for (int k = lane; k < 128; k += 64) tw_st64(((uint32_t)k << 4 | (uint32_t)hs << 3) + TW_XY, x_none, 0u);
 				for (int k = lane; k < 65; k += 64) tw_st32(mkb + ((uint32_t)k << 2), -1);
 				wave_mem_fence();
-				c_xcarry = 0;
 				if (lane == 0) tw_st32(sa + TW_CARRY + 12u, 0);
 				if (take_tile(tl_x, tl_y) > 0) goes_on = true;                 // (a unit has at least two anchors: always)
 				TW_STAMP_C(if (g.stamp) { st_tail += (unsigned int)(TW_NOW() - tc2); ++st_unit; })
@@ -664,7 +655,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 			} else retired |= hm;
 			if (lane == 0) {
 				tw_st64(sa, (uint32_t)c_next, (uint32_t)((uint64_t)c_next >> 32)); tw_st64(sa + 8u, (uint32_t)c_base, (uint32_t)((uint64_t)c_base >> 32));
-				tw_st64(sa + 16u, (uint32_t)c_xcarry, (uint32_t)(c_xcarry >> 32)); tw_st64(sa + 24u, (uint32_t)c_rel0, (uint32_t)c_room);
+				tw_st64(sa + 24u, (uint32_t)c_rel0, (uint32_t)c_room);
 				tw_st64(sa + 32u, (uint32_t)c_read, (uint32_t)c_tile0);
 			}
 		}
