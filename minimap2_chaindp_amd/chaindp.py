@@ -548,6 +548,15 @@ class Device:
         self._lib.chaindp_debug_leftover.argtypes = [C.c_void_p]
         return int(self._lib.chaindp_debug_leftover(self._ctx))
 
+    def seed_route(self):
+        """How the last collect_seeds was routed (read-only test hook): dict of max_n, max_n2, lab_cap (the limits the context settled
+        on when it first collected seeds), items (buckets k_seed_sort_huge handed to the LDS sort) and tied (units with equal x)."""
+        self._lib.chaindp_debug_seed_route.restype = C.c_int
+        self._lib.chaindp_debug_seed_route.argtypes = [C.c_void_p, C.c_void_p]
+        out = (C.c_int64 * 5)()
+        self._check(self._lib.chaindp_debug_seed_route(self._ctx, out))
+        return dict(zip(("max_n", "max_n2", "lab_cap", "items", "tied"), (int(x) for x in out)))
+
     def device_bytes(self):
         """Bytes of device memory the context owns at this moment (test hook)."""
         self._lib.chaindp_debug_device_bytes.restype = C.c_int64

@@ -83,6 +83,7 @@ struct chaindp_ctx {
 	int64_t seed_cap_mini = 0, n_mini_pos = 0;
 	int seed_max_n = -1, seed_max_n2 = -1; // largest reads the two configurations of the LDS sort take on this device
 	int seed_lab_cap = 0;                  // digits k_seed_sort_huge keeps in LDS
+	bool seed_route_valid = false;         // seed.totals[2..3] are the last collection's (chaindp_debug_seed_route): its sort was launched
 	// chains to hits (allocated on first use, grown with the batch)
 	void *d_regs = nullptr, *d_reg_counts = nullptr, *d_ref_len = nullptr, *d_mp_up = nullptr;
 	size_t regs_cap = 0, reg_counts_cap = 0, ref_len_cap = 0, mp_up_cap = 0;
@@ -765,6 +766,26 @@ extern "C" int64_t chaindp_debug_deep_units(chaindp_ctx_t *ctx)
 // test hook (not in the public header): bytes of device memory the context owns at this moment
 extern "C" int64_t chaindp_debug_device_bytes(chaindp_ctx_t *ctx) { return ctx ? (int64_t)ctx->pool.bytes() : -1; }
 
+// test hook (not in the public header; read-only): how the last seed collection was routed -- out[0..2] = the limits the context
+// settled on when its first collection reached the sort (max_n, max_n2: the largest reads the two configurations of the LDS sort take;
+// lab_cap: digits k_seed_sort_huge keeps in LDS; -1 / -1 / 0 before that), out[3] = buckets k_seed_sort_huge handed to the LDS sort as
+// work items, out[4] = units (reads and work items) with equal x that went through the reference's procedure in the second launch.
+// The two counts are 0 where the last collection launched no sort (no reads, an error before the sort, no collection yet).
+extern "C" int chaindp_debug_seed_route(chaindp_ctx_t *ctx, int64_t out[5])
+{
+	if (!ctx) return CHAINDP_ERR_ARG;
+	if (!out) { ctx->err = "chaindp_debug_seed_route: no output array"; return CHAINDP_ERR_ARG; }
+	unsigned long long c[2] = {0, 0};
+	if (ctx->seed_route_valid && ctx->seed.totals) {
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		HIP_TRY(ctx, hipMemcpy(c, ctx->seed.totals + 2, sizeof(c), hipMemcpyDeviceToHost));
+	}
+	out[0] = ctx->seed_max_n; out[1] = ctx->seed_max_n2; out[2] = ctx->seed_lab_cap;
+	out[3] = (int64_t)c[0]; out[4] = (int64_t)c[1];
+	return CHAINDP_OK;
+}
+
 // test hook (not in the public header): copies one of the backtrack scratch arrays to the host
 extern "C" int chaindp_debug_bottom(chaindp_ctx_t *ctx, int which, void *dst, size_t bytes)
 {
@@ -1036,6 +1057,7 @@ static int collect_seeds_impl(chaindp_ctx *ctx, const chaindp_index_t *ix, int f
 	if (n_mini < 0 || (n_mini > 0 && !mini && !read_mini && !resident)) { ctx->err = "bad minimizers"; return CHAINDP_ERR_ARG; }
 	if (n_reads > ctx->cap_reads) { ctx->err = "batch exceeds the capacity the context was created with"; return CHAINDP_ERR_CAPACITY; }
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	ctx->seed_route_valid = false;
 	int rc = seed_reserve(ctx, n_mini);
 	if (rc) return rc;
 	hipStream_t st = ctx->stream;
@@ -1087,6 +1109,7 @@ static int collect_seeds_impl(chaindp_ctx *ctx, const chaindp_index_t *ix, int f
 	HIP_TRY(ctx, chaindp::launch_seed_expand_sort(st, dix, flag, n_reads, n_mini, ctx->d_mini_off, ctx->d_mini, ctx->d_bid, ctx->d_qlen, ctx->seed,
 	                                              ctx->d_seeds, ctx->d_a, ctx->d_off, ctx->d_mini_pos, ctx->seed_max_n, ctx->seed_max_n2,
 	                                              ctx->seed_lab_cap, (int64_t)totals[0]));
+	ctx->seed_route_valid = n_reads > 0;                           // (the sort clears its two counters when it has reads)
 	if (off) HIP_TRY(ctx, hipMemcpyAsync(off, ctx->d_off, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
 	if (mini_pos_off) HIP_TRY(ctx, hipMemcpyAsync(mini_pos_off, ctx->d_mp_off, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
 	if (rep_len && n_reads) HIP_TRY(ctx, hipMemcpyAsync(rep_len, ctx->d_rep_len, (size_t)n_reads * 4, hipMemcpyDeviceToHost, st));

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+import seed_edge_shapes as ss
 from minimap2_chaindp_amd import chaindp, params as P
 
 pytestmark = pytest.mark.gpu
@@ -108,54 +109,10 @@ def test_gpu_seed_collection_at_scale():
 
 def _build_image(rng, n_keys, max_cnt, b_bits=6, rid_pool=None, pos_bits=21):
     """A synthetic index image in the reference's FPGA layout (index.c:603-720): random minimizers with 1..max_cnt positions,
-    hashed into 2^b_bits buckets with khash's own probing (khash.h:218-231).  Returns (blobs, minimizer values)."""
-    keys = rng.choice(1 << 34, size=n_keys, replace=False).astype(np.uint64) + np.uint64(1)
-    buckets = [[] for _ in range(1 << b_bits)]
-    for m in keys:
-        buckets[int(m) & ((1 << b_bits) - 1)].append(int(m))
-    B, H, V, Pa = bytearray(), bytearray(), bytearray(), bytearray()
-    allh = allp = 0
-    for bk in buckets:
-        if not bk:
-            B += (0).to_bytes(16, "little")
-            continue
-        nb = 4
-        while nb < 2 * len(bk):
-            nb <<= 1
-        slots_k, slots_v, used, p_local = [0] * nb, [0] * nb, [False] * nb, []
-        for m in bk:
-            cnt = int(rng.integers(1, max_cnt + 1))
-            pos = [int(rng.integers(0, rid_pool or 1 << 20)) << 43 | int(rng.integers(0, 1 << pos_bits)) << 22 | int(rng.integers(0, 2)) << 21 | int(rng.integers(0, 1 << 10))
-                   for _ in range(cnt)]
-            key = (m >> b_bits) << 1
-            i, step = (key >> 1) & (nb - 1), 0
-            while used[i]:
-                step += 1
-                i = (i + step) & (nb - 1)
-            used[i] = True
-            if cnt == 1:
-                slots_k[i], slots_v[i] = key | 1, pos[0]
-            else:
-                slots_k[i], slots_v[i] = key, len(p_local) << 32 | cnt
-                p_local += pos
-        tmp_nb = (nb + 7) & ~7
-        B += (((allp & 0xff) << 56) | (nb << 24)).to_bytes(8, "little") + ((allh << 28) | (allp >> 8)).to_bytes(8, "little")
-        flags = [0] * max(1, nb >> 4)
-        for i in range(nb):
-            if not used[i]:
-                flags[i >> 4] |= 2 << ((i & 15) << 1)                 # "empty" (khash.h:166)
-        for g0 in range(0, tmp_nb, 8):
-            H += (flags[g0 >> 4] & 0xffffffff).to_bytes(4, "little")
-            for i in range(g0, g0 + 8):
-                H += ((slots_k[i] if i < nb else 0) & 0xffffffffffff).to_bytes(6, "little")
-                V += ((slots_v[i] if i < nb else 0)).to_bytes(8, "little")
-            H += bytes(12)
-        for x in p_local:
-            Pa += x.to_bytes(8, "little")
-        allh += tmp_nb
-        allp += len(p_local)
-    blobs = [np.frombuffer(bytes(x), np.uint8).copy() for x in (B, H, V, Pa)]
-    return blobs, keys
+    hashed into 2^b_bits buckets with khash's own probing (khash.h:218-231); the layout itself is written once, in
+    seed_edge_shapes.build_image.  Returns (blobs, minimizer values)."""
+    table, keys = ss.random_table(rng, n_keys, max_cnt, b_bits=b_bits, rid_pool=rid_pool, pos_bits=pos_bits)
+    return ss.build_image(table, b_bits)[0], keys
 
 
 def _synthetic_case(seed, max_cnt, n_mini, rep_pct, rid_pool=None, pos_bits=21, quiet=False):
