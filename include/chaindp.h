@@ -180,6 +180,29 @@ int chaindp_collect_seeds_gather(chaindp_ctx_t *ctx, const chaindp_index_t *idx,
 int chaindp_scatter_mini_pos(chaindp_ctx_t *ctx, int64_t n_reads, uint64_t *const *dst);
 int chaindp_download_anchors(chaindp_ctx_t *ctx, chaindp_anchor_t *a);      /* the resident batch's anchors */
 
+/* ---- the index image built on the GPU: target bases in, B/H/V/P resident ----------------------------------------------------
+ * mm_idx_gen (index.c:541-725: the index-side mm_sketch with rid = the sequence's number, worker_post's sort, grouping and khash
+ * tables, and the FPGA image of index.c:603-720) for ONE index part, on ctx's device.  seq / seq_off as chaindp_sketch takes them;
+ * rank[n_seqs] = rank of each sequence's name in strcmp order (mi->rever_rid), NULL = the sequence number.  b = bucket bits (mi->b).
+ * Returns an index every call that takes a chaindp_index_t accepts, or NULL (chaindp_last_error(ctx)).  Uses ctx's sketch buffers:
+ * like chaindp_sketch it starts a new batch in ctx (and leaves no minimizers for the mapping calls).  Synchronous.
+ * The image is the reference's in CANONICAL form: B, P, every flag word, the padding and key and value of every occupied slot are
+ * the reference's byte for byte; key and value of an empty slot are zero (the reference writes whatever its heap held there).
+ * Refused (NULL; the code is CHAINDP_ERR_ARG's, the context stays usable): b outside 1..24, w or k outside what chaindp_sketch takes,
+ * more than 2^21 sequences, a sequence of 2^21 bases or more, a rank of 2^21 or more -- the image has 21 bits for each.  It also
+ * returns NULL when the device has no room or a blob would pass the 36-bit offsets of B (CHAINDP_ERR_CAPACITY's message).
+ * An empty input (n_seqs == 0, or no minimizer at all) gives 2^b zero B entries and empty H, V, P. */
+chaindp_index_t *chaindp_index_build(chaindp_ctx_t *ctx, int w, int k, int b, int is_hpc, int64_t n_seqs,
+                                     const int64_t *seq_off, const char *seq, const uint32_t *rank);
+int chaindp_index_build_status(const chaindp_ctx_t *ctx);    /* the CHAINDP_* code of the last chaindp_index_build on ctx */
+/* Sizes in bytes and contents of the blobs B, H, V, P of any index: of a built one, or what chaindp_index_create was given. */
+int chaindp_index_sizes(const chaindp_index_t *idx, size_t bytes[4]);
+int chaindp_index_download(const chaindp_index_t *idx, void *B, void *H, void *V, void *P);   /* any may be NULL */
+/* mm_idx_cal_max_occ (index.c:307-328): INT32_MAX for f <= 0, else 1 + the (uint32_t)((1. - f) * n)-th smallest (0-based) of the
+ * occurrence counts of the n distinct minimizers; works on any index, built or created from blobs (CHAINDP_ERR_ARG for one without a
+ * minimizer).  This is where a caller gets mid_occ for chaindp_collect_seeds from (mm_mapopt_update, options.c). */
+int chaindp_index_cal_max_occ(const chaindp_index_t *idx, float f, int32_t *max_occ);
+
 /* ---- the whole resident pipeline in one call: minimizers in, hits out (SURVEY 8f N2 -> 8a -> N1 -> N4) -----------
  * What the reference does per read between collect_minimizers and chain_post (map.c:350-366 on the host, 484-568 on the device,
  * 862 on the host again): collect_seed_hits over the index image, mm_chain_dp_fpga, mm_chain_dp_bottom, mm_gen_regs -- here
@@ -264,7 +287,8 @@ int chaindp_map_reads(chaindp_ctx_t *ctx, const chaindp_index_t *idx, int flag, 
  * until a new batch has been collected and run.  Download what you need of a batch before sketching the next one in the same context.
  * The buffers grow with the batch (about 45 bytes per base); CHAINDP_ERR_CAPACITY if the batch has more reads than ctx was created
  * for, 2^31 bases or more, or more than the device has room for -- the context stays usable.
- * Not done here: mm_dust_minier (opt->sdust_thres is 0 in every preset), the index-side sketch, 2-bit packed input.  Synchronous. */
+ * Not done here: mm_dust_minier (opt->sdust_thres is 0 in every preset), 2-bit packed input.  Synchronous.  (The index-side sketch is
+ * part of chaindp_index_build.) */
 int chaindp_sketch(chaindp_ctx_t *ctx, int w, int k, int is_hpc, int64_t n_seqs, const int64_t *seq_off, const char *seq,
                    const int32_t *n_segs_per_read, int64_t *mini_off /* [n_reads + 1] */);
 int chaindp_download_minimizers(chaindp_ctx_t *ctx, chaindp_anchor_t *mini);   /* mini_off[n_reads] entries */

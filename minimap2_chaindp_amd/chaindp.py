@@ -32,6 +32,7 @@ ABI_SYMBOLS = (
     "chaindp_chain_post", "chaindp_map_reads", "chaindp_post_logf_selftest", "chaindp_post_logf_patches",
     "chaindp_sketch", "chaindp_download_minimizers", "chaindp_map_seqs", "chaindp_get_sketch_ms",
     "chaindp_frag_post", "chaindp_map_frags", "chaindp_map_frag_seqs",
+    "chaindp_index_build", "chaindp_index_build_status", "chaindp_index_sizes", "chaindp_index_download", "chaindp_index_cal_max_occ",
 )
 
 # chaindp_reg_t == mm_reg1_t (minimap.h:100-115), 80 bytes; `bits` is the bit-field word (rev = bit 10)
@@ -87,6 +88,17 @@ def lib():
         L.chaindp_index_create.argtypes = [i32, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
         L.chaindp_index_destroy.restype = None
         L.chaindp_index_destroy.argtypes = [vp]
+        L.chaindp_index_build.restype = vp
+        L.chaindp_index_build.argtypes = [vp, i32, i32, i32, i32, i64, vp, vp, vp]
+        L.chaindp_index_build_status.argtypes = [vp]
+        L.chaindp_index_sizes.argtypes = [vp, vp]
+        L.chaindp_index_download.argtypes = [vp, vp, vp, vp, vp]
+        L.chaindp_index_cal_max_occ.argtypes = [vp, C.c_float, vp]
+        L.chaindp_debug_index_from_minimizers.restype = vp
+        L.chaindp_debug_index_from_minimizers.argtypes = [vp, i32, i64, vp, i64, vp]
+        L.chaindp_debug_index_chunk_bases.argtypes = [vp, i64]
+        L.chaindp_debug_index_route.argtypes = [vp, vp]
+        L.chaindp_debug_index_stage_ms.argtypes = [vp, vp]
         L.chaindp_collect_seeds.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
         L.chaindp_download_mini_pos.argtypes = [vp, vp]
         L.chaindp_collect_seeds_gather.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -278,6 +290,65 @@ class Device:
             raise ChainDPError((self._lib.chaindp_last_error(None) or b"").decode())
         self._indexes.append(h)
         return h
+
+    # -- the index image built on the device (chaindp_index_build): what replaces the reference's mm_idx_gen
+    INDEX_ROUTE = ("sub_batches", "minimizers", "distinct", "buckets", "expanded", "max_keys", "passes_run", "passes_skipped")
+
+    def build_index(self, w, k, is_hpc, seq, seq_off, rank=None, b=14):
+        """Target sequences (bytes or uint8, concatenated; seq_off int64[n_seqs+1]) -> a handle like load_index's, the image built on the
+        device in the reference's canonical form.  rank[n_seqs]: each sequence's rank by name (None: its number); b: bucket bits."""
+        seq, seq_off = self._seqs(seq, seq_off)
+        rk = None if rank is None else np.ascontiguousarray(rank, np.uint32)
+        if rk is not None and len(rk) != len(seq_off) - 1:
+            raise ChainDPError("rank needs one entry per sequence")
+        h = self._lib.chaindp_index_build(self._ctx, int(w), int(k), int(b), int(bool(is_hpc)), len(seq_off) - 1, _ptr(seq_off),
+                                          _ptr(seq) if len(seq) else None, None if rk is None or not len(rk) else _ptr(rk))
+        if not h:
+            self._check(self._lib.chaindp_index_build_status(self._ctx))
+            raise ChainDPError("chaindp_index_build returned no index")
+        self._indexes.append(h)
+        return h
+
+    def index_from_minimizers(self, b, mini, n_seqs=0, rank=None):
+        """Test hook: the build behind the sketch, from minimizers uint64[n, 2] of the caller's."""
+        mini = np.ascontiguousarray(mini, np.uint64).reshape(-1, 2)
+        rk = None if rank is None else np.ascontiguousarray(rank, np.uint32)
+        h = self._lib.chaindp_debug_index_from_minimizers(self._ctx, int(b), len(mini), _ptr(mini) if len(mini) else None,
+                                                          int(n_seqs if rk is None else len(rk)), None if rk is None or not len(rk) else _ptr(rk))
+        if not h:
+            raise ChainDPError((self._lib.chaindp_last_error(self._ctx) or b"").decode())
+        self._indexes.append(h)
+        return h
+
+    def set_index_chunk_bases(self, n=0):
+        """Test hook: bases per sketch sub-batch of build_index (0: as many as a sketch takes)."""
+        self._check(self._lib.chaindp_debug_index_chunk_bases(self._ctx, int(n)))
+
+    def index_blobs(self, index):
+        """[B, H, V, P] (uint8 arrays) of any index handle."""
+        nb = (C.c_size_t * 4)()
+        self._check(self._lib.chaindp_index_sizes(index, nb))
+        blobs = [np.zeros(int(n), np.uint8) for n in nb]
+        self._check(self._lib.chaindp_index_download(index, *[_ptr(x) if x.size else None for x in blobs]))
+        return blobs
+
+    def index_max_occ(self, index, f):
+        """mm_idx_cal_max_occ(mi, f) of any index handle."""
+        out = C.c_int32(0)
+        self._check(self._lib.chaindp_index_cal_max_occ(index, float(f), C.byref(out)))
+        return int(out.value)
+
+    def index_route(self, index):
+        """What the build of `index` did: a dict over INDEX_ROUTE."""
+        out = np.zeros(8, np.int64)
+        self._check(self._lib.chaindp_debug_index_route(index, _ptr(out)))
+        return dict(zip(self.INDEX_ROUTE, out.tolist()))
+
+    def index_stage_ms(self, index):
+        """Milliseconds the build of `index` spent: (sketch sub-batches with their uploads, host clock; sort; grouping; tables -- device)."""
+        ms = np.zeros(4, np.float64)
+        self._check(self._lib.chaindp_debug_index_stage_ms(index, _ptr(ms)))
+        return ms.tolist()
 
     def collect_seeds(self, index, flag, max_occ, mini_off, mini, bid, qlen, n_segs=None):
         """Minimizers of a batch -> sorted anchors resident on the device (as after upload()).  Returns (off int64[n_reads+1],

@@ -262,6 +262,31 @@ hipError_t launch_sketch_count(hipStream_t st, const SketchArgs &a, int64_t n_re
                                unsigned long long *d_totals);
 hipError_t launch_sketch_emit(hipStream_t st, const SketchArgs &a, int64_t n_bases, void *d_mini, int64_t mini_cap);
 
+// the index image built on the device (chaindp_index.hip): minimizers of the target in, blobs B, H, V, P out
+#define IX_TILE 1024                 // records per workgroup of a radix pass
+struct IndexScratch {                // n = minimizers, nb = 2^b buckets
+	unsigned long long *hist;        // 256 x ceil(n / IX_TILE): digit counts per tile, scanned in place
+	unsigned long long *scan_tmp;    // scratch of the scans: max(256 x tiles, nb) / 1024 + 2
+	unsigned long long *bits;        // 4: OR and AND of the records' first words, OR and AND of their second words
+	uint32_t *bk_keys, *bk_p;        // nb each: distinct minimizers / P words of every bucket
+	unsigned long long *bk_start;    // nb: first record of every non-empty bucket
+	unsigned long long *bk_h, *bk_pp;// nb each: slots (rounded up to eight) / P words per bucket, scanned in place: allh, allp of index.c:612-632
+	unsigned long long *totals;      // 8: slots, P words, distinct minimizers, non-empty buckets, buckets expanded, most keys in a bucket
+};
+// records (m rotated right by b inside 56 bits, y) from the minimizers, and sc.bits (the host presets bits[] to 0, ~0, 0, ~0)
+hipError_t launch_index_prepare(hipStream_t st, int b, int64_t n, const void *d_mini, void *d_rec, unsigned long long *d_bits);
+// one stable pass over the byte at `shift` of word 0 (x) or 1 (y) of every record
+hipError_t launch_index_sort_pass(hipStream_t st, int64_t n, const void *d_src, void *d_dst, int word, int shift, unsigned long long *d_hist,
+                                  unsigned long long *d_scan_tmp, unsigned long long *d_total);
+// sorted records -> per-bucket counts, sc.totals, sc.bk_h / sc.bk_pp (scanned) and the B blob (nb x 16 bytes)
+hipError_t launch_index_group(hipStream_t st, int b, int64_t n, const void *d_rec, IndexScratch sc, void *d_B);
+// the hash tables, values and position words into the zero-filled H, V, P; d_occ_a / d_occ_b: totals[0] / 8 zeroed bytes each.
+// d_rank[n_seqs] may be NULL (rank = sequence number)
+hipError_t launch_index_tables(hipStream_t st, int b, int64_t n, const void *d_rec, IndexScratch sc, const uint32_t *d_rank, int64_t n_seqs,
+                               void *d_H, void *d_V, void *d_P, uint8_t *d_occ_a, uint8_t *d_occ_b);
+// d_counts[nV / 8] (zeroed): occurrences of every occupied slot's minimizer; *d_bad (zeroed) is set if B points outside the blobs
+hipError_t launch_index_counts(hipStream_t st, const SeedIndex &ix, uint32_t *d_counts, unsigned *d_bad);
+
 // zero-copy movement between device-visible (pinned) host buffers and HBM: chaindp_io.hip
 hipError_t launch_gather_reads(hipStream_t st, int64_t n_reads, const int64_t *d_off, const void *const *d_src, void *d_a);
 hipError_t launch_scatter_seeds(hipStream_t st, int64_t n_reads, const int64_t *d_seeds_off, void *const *d_dst, const void *d_seeds);

@@ -27,8 +27,9 @@
 //            the minimizers at their offsets: the order is the slot order, no atomic is involved.
 //
 // Tiles of bases never straddle sequences (the host lists the 256-base chunks of every sequence, an empty sequence gets one empty
-// chunk), tiles of slots do: a slot carries its sequence.  Out of scope: mm_dust_minier (sdust_thres is 0 in every preset), the
-// index-side sketch, 2-bit packed input, sequence packets through the fpga_* shim.
+// chunk), tiles of slots do: a slot carries its sequence.  The index-side sketch (mm_idx_gen's, rid = the sequence's number) is the same
+// kernels with another seq_ybase (chaindp_index_build).  Out of scope: mm_dust_minier (sdust_thres is 0 in every preset), 2-bit packed
+// input, sequence packets through the fpga_* shim.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "chaindp_kernels.h"
