@@ -1,0 +1,204 @@
+// chaindp_ctx.h -- what the translation units of the host ABI (chaindp_abi*.cpp) share: the context, the index image, HIP_TRY and
+// the helpers and stage entry points that more than one stage uses.  Host only; nothing else includes it.
+#ifndef CHAINDP_CTX_H
+#define CHAINDP_CTX_H
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <initializer_list>
+#include <string>
+#include <vector>
+#include "../../include/chaindp.h"
+#include "chaindp_kernels.h"
+#include "chaindp_devmem.h"
+
+struct EventSet { hipEvent_t e[3]; int n; int slot0; };  // e[0..n): consecutive kernel boundaries; slot0 = first ms[] index
+
+struct chaindp_ctx {
+	int device = -1;
+	// every device buffer below is an entry of this pool: allocated, grown and freed through it and nowhere else
+	chaindp::DevPool pool{[](void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }, [](void *p) { return (int)hipFree(p); }};
+	hipStream_t stream = nullptr;
+	int64_t cap_anchors = 0, cap_reads = 0;
+	int ring = 128;
+	// resident batch
+	int64_t n_reads = 0, total = 0, n_seeds = 0;
+	bool has_n_segs = false, ran = false;
+	bool singles_pending = false;    // the last run left f, p, v, flags[] of its singletons to k_fill_singles (chaindp_download runs it)
+	chaindp_params_t ran_par{};      // the parameters of that run
+	int64_t *d_off = nullptr;
+	void *d_a = nullptr;
+	int32_t *d_n_segs = nullptr;
+	int32_t *d_f = nullptr, *d_p = nullptr, *d_v = nullptr;
+	// scratch
+	unsigned long long *d_tg = nullptr;   // deep-path marks, tagged with the run epoch (never re-initialised)
+	uint32_t epoch = 0;
+	unsigned long long *d_sumq = nullptr;
+	chaindp::Unit *d_units = nullptr;
+	chaindp::UnitAux *d_unit_aux = nullptr;   // per unit, beside d_units: what k_chain_twin needs to pick it up without further loads
+	chaindp::Unit *d_left = nullptr;          // units the two-per-wave kernel hands over to k_chain_units
+	unsigned long long *d_left_cnt = nullptr; // the four hand-over words: counts, queue words and the route flag (HandoverWords, below)
+	chaindp::Unit *d_deep = nullptr;          // units k_chain_units hands over to its k_chain_dense (scans that keep reaching past the ring)
+	int deep_route = 0;                   // test hook: 1 k_chain_dense, 2 k_chain_dense1 whatever the batch looks like
+	int deep_eager = 0;                   // test hook: hand over any unit with a few deep scans, whatever its length
+	bool deep_handover = true;            // CHAINDP_NO_DEEP_HANDOVER (diagnostic / A-B): every unit stays in the launch that took it
+	bool use_quad = false;                // CHAINDP_QUAD=1 / chaindp_debug_set_quad (A/B, tests): one-table batches of ordinary units four per wave
+	                                      // (k_chain_quad: correct, measured slower than k_chain_twin -- DESIGN.md section 6 -- so off by default)
+	int twin_two_tables = 0;              // chaindp_debug_set_twin_tables (tests): 1 keeps one-key batches on k_chain_twin's two-table layout
+	int twin_force_left = 0;              // CHAINDP_TWIN_FORCE_LEFT / chaindp_debug_set_twin_handover (tests): 1 k_chain_twin hands every unit
+	                                      // over untouched, 2 after its first tile (k_chain_units resumes there); the variable is read once, at chaindp_create
+	int variant = 0;                      // 0: k_chain_twin + k_chain_units for the rest; 1: k_chain_units, general variant; 2: k_chain_units only
+	unsigned long long *d_counters = nullptr;
+	chaindp::PrepassScratch pre = {nullptr, nullptr, nullptr, nullptr, nullptr};
+	chaindp::CompactScratch cmp = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+	chaindp::BottomScratch bot = {};
+	// first-use groups of buffers: each flag is set once, after its group's allocations have all succeeded, and never reset
+	bool compact_ready = false, bot_ready = false, seed_ready = false, regs_ready = false, post_ready = false, logf_ready = false;
+	chaindp::DevGrow lut;            // uint16_t[]: the per-read gap-cost tables of the fast variant
+	chaindp::DevGrow ptrs;           // void*[]: per-read host pointers for the gather / scatter kernels
+	bool use_lut = true;
+	// compaction (allocated on first use)
+	int32_t *d_first_child = nullptr;
+	unsigned int *d_twin_queue = nullptr;   // k_chain_twin's eight grab counters, a cache line apart (2 KB)
+	int64_t *d_seeds_off = nullptr;
+	void *d_seeds = nullptr;
+	// seed collection (allocated on first use, grown with the batch)
+	chaindp::SeedScratch seed = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+	void *d_mini = nullptr;
+	int64_t *d_mini_off = nullptr, *d_mp_off = nullptr;
+	uint32_t *d_bid = nullptr;
+	int32_t *d_qlen = nullptr, *d_rep_len = nullptr;
+	unsigned long long *d_mini_pos = nullptr;
+	int64_t seed_cap_mini = 0, n_mini_pos = 0;
+	int seed_max_n = -1, seed_max_n2 = -1; // largest reads the two configurations of the LDS sort take on this device
+	int seed_lab_cap = 0;                  // digits k_seed_sort_huge keeps in LDS
+	bool seed_route_valid = false;         // seed.totals[2..3] are the last collection's (chaindp_debug_seed_route): its sort was launched
+	// chains to hits (allocated on first use, grown with the batch)
+	chaindp::DevGrow regs, reg_counts, ref_len, mp_up;
+	uint32_t *d_rhash = nullptr;
+	int32_t *d_rqlen = nullptr;
+	int64_t *d_regs_off = nullptr, *d_mp_off_up = nullptr;
+	unsigned long long *d_sum_k = nullptr;
+	int64_t bot_n_reads = -1, bot_n_chains = 0, bot_n_b = 0;   // what the last chaindp_backtrack left resident (-1: nothing of this batch)
+	bool mp_resident = false;                                  // this batch's mini_pos are on the device (it came from chaindp_collect_seeds)
+	bool regs_resident = false;      // regs / d_rqlen hold what chaindp_gen_regs made of the resident chains (chaindp_est_err's upload clears it)
+	// chain_post + mm_set_mapq (allocated on first use, grown with the batch)
+	chaindp::DevGrow post_stage, post_out, post_sq, post_scratch;
+	unsigned long long *d_post_off = nullptr, *d_post_tile = nullptr;
+	int32_t *d_post_qlen = nullptr, *d_post_rep = nullptr, *d_post_err = nullptr;
+	uint32_t *d_logf_k = nullptr;
+	float *d_logf_v = nullptr;
+	int n_logf = 0;
+	// reads of several segments: chaindp_frag_post (allocated on first use, grown with the batch)
+	chaindp::DevGrow frag_seq, frag_cnt, frag_u, frag_a, frag_stage, frag_z, frag_stacks, frag_out;
+	int frag_lds_cap = FRAG_LDS_CAP;           // chaindp_debug_set_frag_lds_cap (tests): fewer hits per fragment stay in LDS
+	// sketch (allocated on first use, grown with the batch)
+	chaindp::SketchArgs sk = {};
+	int64_t sk_cap_bases = -1, sk_cap_chunks = -1, sk_cap_seqs = -1;
+	int64_t sk_max_bases = 0x7fffff00;         // CHAINDP_SKETCH_MAX_BASES (test switch) lowers it; positions and ranks are 32-bit
+	unsigned long long *d_sk_totals = nullptr;
+	bool sk_valid = false;                     // d_mini / d_mini_off hold what the last chaindp_sketch made
+	int64_t sk_n_reads = 0, sk_n_mini = 0;
+	int ix_status = 0;                         // code of the last chaindp_index_build (chaindp_index_build_status)
+	int64_t ix_chunk_bases = 0;                // chaindp_debug_index_chunk_bases (tests): bases per sketch sub-batch of an index build, 0 = sk_max_bases
+	std::vector<int64_t> sk_mini_off;          // its mini_off and the reads' lengths, for the calls that say "the resident ones"
+	std::vector<int32_t> sk_qlen;
+	std::vector<int32_t> sk_seq_len;           // ... and the lengths of its sequences (the segments of chaindp_frag_post)
+	hipEvent_t sk_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around the two phases of a sketch while profiling is on (created once)
+	double sk_ms = 0;
+	int64_t sk_calls = 0;
+	// profiling
+	bool prof = false;
+	std::vector<EventSet> pending;
+	double ms[4] = {0, 0, 0, 0};
+	int64_t launches[4] = {0, 0, 0, 0};
+	int64_t stats[4] = {0, 0, 0, 0};
+	std::string err;
+};
+
+struct chaindp_index {
+	int device = -1;
+	uint8_t *blob[4] = {nullptr, nullptr, nullptr, nullptr};
+	size_t bytes[4] = {0, 0, 0, 0};
+	int b_bits = 0;
+	bool built = false;              // made by chaindp_index_build / chaindp_debug_index_from_minimizers
+	int64_t route[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // what the build did (chaindp_debug_index_route)
+	double stage_ms[4] = {0, 0, 0, 0};             // sketch sub-batches with their uploads (host clock); sort, grouping, tables (device, events)
+};
+
+// (ctx: a context or a pipe)
+#define HIP_TRY(ctx, call)                                                                         \
+	do {                                                                                           \
+		hipError_t e_ = (call);                                                                    \
+		if (e_ != hipSuccess) {                                                                    \
+			(ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                        \
+			return CHAINDP_ERR_HIP;                                                                \
+		}                                                                                          \
+	} while (0)
+
+// The four 64-bit hand-over words of a run (chaindp_ctx::d_left_cnt), zeroed together by the prepass' first kernel:
+//   word 0  low half: units k_chain_twin / k_chain_quad handed over to k_chain_units (d_left; 0xffffffff = the twin kernel declined
+//           the batch, every unit); high half: the twin / quad kernel's queue word
+//   word 1  low half: units k_chain_units handed over to the dense kernels (d_deep)
+//   word 2  k_chain_dense1's two queues, one per half
+//   word 3  low half: the route flag, 1 = k_chain_quad took the batch, 2 / 3 = k_chain_twin with one / two cost tables; high half:
+//           the queue word of k_chain_dense / k_chain_dense16
+// Each accessor has the type the launcher that takes it declares; the *_word ones are also what the debug getters read back.
+struct HandoverWords {
+	unsigned long long *w;
+	explicit HandoverWords(const chaindp_ctx *ctx) : w(ctx->d_left_cnt) {}
+	unsigned long long *all() const { return w; }                                // launch_prepass, which zeroes the four
+	unsigned long long *left_word() const { return w; }
+	unsigned int *left_count() const { return (unsigned int*)w; }
+	unsigned int *left_queue() const { return (unsigned int*)w + 1; }
+	unsigned long long *deep_word() const { return w + 1; }
+	unsigned int *deep_count() const { return (unsigned int*)(w + 1); }
+	unsigned int *dense1_queues() const { return (unsigned int*)(w + 2); }
+	unsigned long long *route_word() const { return w + 3; }
+	unsigned int *route() const { return (unsigned int*)(w + 3); }
+	unsigned int *dense_queue() const { return (unsigned int*)(w + 3) + 1; }
+};
+
+namespace chaindp {
+
+extern thread_local std::string g_create_error;     // what chaindp_last_error(NULL) / chaindp_pipe_last_error(NULL) return
+
+// ---- helpers (chaindp_abi.cpp unless noted)
+int first_use(chaindp_ctx *ctx, bool &ready, const char *what, std::initializer_list<DevBuf> bufs);
+hipError_t dev_grow(chaindp_ctx *ctx, DevGrow &g, size_t need);
+void begin_batch(chaindp_ctx *ctx, int64_t n_reads, int64_t total, bool mp_resident = false);
+hipError_t stage_n_segs(chaindp_ctx *ctx, const int32_t *n_segs_per_read, int64_t n_reads, hipStream_t st);
+hipError_t prof_begin(chaindp_ctx *ctx, EventSet &es, int n, int slot0, hipStream_t st);
+hipError_t prof_mark(chaindp_ctx *ctx, EventSet &es, int k, hipStream_t st);
+Params to_params(const chaindp_params_t *p);
+int check_params(chaindp_ctx *ctx, const chaindp_params_t *par);
+int check_batch(const chaindp_ctx *ctx, int64_t n_reads, const int64_t *off, const void *payload, bool per_read, const char *owner,
+                std::string &err, int64_t &total);
+int stage_pointers(chaindp_ctx *ctx, const void *const *ptrs, int64_t n);
+// chaindp_abi_hits.cpp
+int regs_per_read_buffers(chaindp_ctx *ctx);
+int mini_pos_check(chaindp_ctx *ctx, const int64_t *mini_pos_off, const uint64_t *mini_pos);
+int stage_mini_pos(chaindp_ctx *ctx, int64_t R, const int64_t *mini_pos_off, const uint64_t *mini_pos, const int32_t *ref_len, int32_t n_ref,
+                   const int64_t *&d_mpo, const unsigned long long *&d_mp);
+// chaindp_abi_seed.cpp
+int seed_reserve(chaindp_ctx *ctx, int64_t n_mini, bool oom_is_capacity = false);
+// chaindp_abi_post.cpp
+int post_reserve(chaindp_ctx *ctx, int64_t n_c, int64_t n_b);
+PostOpt to_post_opt(const chaindp_post_opt_t *o);
+int post_require_hits(chaindp_ctx *ctx, const char *who);
+int post_stage_rep_len(chaindp_ctx *ctx, const int32_t *rep_len, int64_t R, const int32_t **d_rep);
+int post_finish(chaindp_ctx *ctx);
+
+// ---- stage entry points that other stages call
+int collect_seeds_impl(chaindp_ctx *ctx, const chaindp_index_t *ix, int flag, int max_occ, int64_t n_reads,
+                       const int64_t *mini_off, const chaindp_anchor_t *mini, const chaindp_anchor_t *const *read_mini,
+                       const uint32_t *bid, const int32_t *qlen,
+                       const int32_t *n_segs_per_read, int64_t *off, int32_t *rep_len, int64_t *mini_pos_off);
+int sketch_impl(chaindp_ctx *ctx, int w, int k, int is_hpc, int64_t n_seqs, const int64_t *seq_off, const char *seq,
+                const int32_t *n_segs_per_read, int64_t *mini_off, int pe_ori, int64_t rid_base = -1);
+int gen_regs_impl(chaindp_ctx *ctx, const uint32_t *hash, const int32_t *qlen, chaindp_reg_t *regs, bool download);
+int map_prefix(chaindp_ctx *ctx, const chaindp_index_t *ix, int flag, int max_occ, const chaindp_params_t *par, int min_cnt, int64_t n_reads,
+               const int64_t *mini_off, const chaindp_anchor_t *mini, const uint32_t *bid, const int32_t *&qlen, const int32_t *n_segs_per_read,
+               const uint32_t *hash, int32_t *rep_len, int64_t *n_anchors, int64_t *regs_off, chaindp_reg_t *regs, int64_t regs_cap);
+
+}  // namespace chaindp
+#endif

@@ -12,6 +12,7 @@ namespace chaindp {
 
 struct DevBuf { void **slot; size_t bytes; };
 template <typename T> static inline DevBuf dev_buf(T *&p, size_t bytes) { return DevBuf{(void**)&p, bytes}; }
+struct DevGrow { void *p = nullptr; size_t cap = 0; };      // a grow-only buffer and its capacity in bytes (DevPool::reserve)
 
 class DevPool {
 public:
@@ -51,6 +52,7 @@ public:
 		*slot = q; cap = grown;
 		return 0;
 	}
+	int reserve(DevGrow &g, size_t need, size_t grown, bool free_first) { return reserve(&g.p, g.cap, need, grown, free_first); }
 	void release(void **slot)
 	{
 		DevBuf *b = find(slot);

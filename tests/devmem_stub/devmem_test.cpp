@@ -118,6 +118,23 @@ int main()
 	g_fail_at = 0;
 	CHECK(pool->reserve(&t, tcap, 65, 65 + 65 / 2 + 64, true) == 0 && t && tcap == 161 && g_live == live0);
 
+	// the same two promises through the DevGrow overload, pointer and capacity as one value
+	chaindp::DevGrow dg;
+	CHECK(pool->reserve(dg, 100, 125, false) == 0 && dg.p && dg.cap == 125);
+	memset(dg.p, 0x21, 125);
+	void *const dg0 = dg.p;
+	bytes0 = pool->bytes(); live0 = g_live; frees0 = g_frees;
+	g_fail_at = 1;
+	CHECK(pool->reserve(dg, 200, 250, false) != 0);
+	CHECK(dg.p == dg0 && dg.cap == 125 && pool->bytes() == bytes0 && g_live == live0 && g_frees == frees0);
+	for (int i = 0; i < 125; ++i) CHECK(((unsigned char*)dg.p)[i] == 0x21);
+	g_fail_at = 1;
+	CHECK(pool->reserve(dg, 200, 200, true) != 0);
+	CHECK(dg.p == nullptr && dg.cap == 0 && pool->bytes() == bytes0 - 125 && g_live == live0 - 1);
+	g_fail_at = 0;
+	CHECK(pool->reserve(dg, 200, 200, true) == 0 && dg.p && dg.cap == 200 && g_live == live0 && pool->bytes() == bytes0 - 125 + 200);
+	memset(dg.p, 0x22, 200);
+
 	// release of one slot, of a slot the pool does not know
 	pool->release((void**)&g.b);
 	CHECK(!g.b && g_live == live0 - 1);
@@ -128,7 +145,7 @@ int main()
 	// release_all: nothing live, every slot null, a second call harmless
 	pool->release_all();
 	CHECK(g_live == 0 && pool->bytes() == 0 && pool->mark() == 0);
-	CHECK(!z && all_null(f) && all_null(g) && !r && !t);
+	CHECK(!z && all_null(f) && all_null(g) && !r && !t && !dg.p);
 	pool->release_all();
 	CHECK(g_live == 0 && pool->bytes() == 0);
 	// ... and the pool works again afterwards; what is live when it is destroyed goes with it

@@ -23,7 +23,7 @@ LDS_LIMIT = 160 * 1024
 TPB = 1024
 
 
-# ---------------------------------------------------------------- the limits, from the formulas of chaindp_seed.hip / chaindp_abi.cpp
+# ---------------------------------------------------------------- the limits, from the formulas of chaindp_seed.hip / chaindp_abi_seed.cpp
 
 def table_waves(workers):
     return 16 if workers >= 32 else 4
