@@ -640,18 +640,6 @@ class Device:
         self._lib.chaindp_debug_deep_units.argtypes = [C.c_void_p]
         return int(self._lib.chaindp_debug_deep_units(self._ctx))
 
-    def set_quad(self, on=True):
-        """Test / A-B hook: let k_chain_quad (four units per wave; off by default: measured slower) take the batches it can."""
-        self._lib.chaindp_debug_set_quad.restype = C.c_int
-        self._lib.chaindp_debug_set_quad.argtypes = [C.c_void_p, C.c_int]
-        self._check(self._lib.chaindp_debug_set_quad(self._ctx, int(bool(on))))
-
-    def quad_took(self):
-        """True if k_chain_quad took the last batch (test hook)."""
-        self._lib.chaindp_debug_quad_took.restype = C.c_int
-        self._lib.chaindp_debug_quad_took.argtypes = [C.c_void_p]
-        return int(self._lib.chaindp_debug_quad_took(self._ctx)) == 1
-
     def set_twin_tables(self, two=True):
         """Test hook: True keeps k_chain_twin on its layout with a cost table per half even where the batch has one table key (the
         layout with one table per wave takes such batches otherwise); False lets the device decide."""

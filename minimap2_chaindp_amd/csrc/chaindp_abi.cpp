@@ -122,6 +122,30 @@ extern "C" void chaindp_destroy(chaindp_ctx_t *ctx)
 	delete ctx;
 }
 
+// The rest of DpDevice: the CU count, the stamp buffers of the diagnostic runs that were asked for, and what holds for every DP
+// kernel instantiation on this device -- no static LDS, and room for the most dynamic LDS a launch can ask for.  what: the
+// kernel an error is about.
+static hipError_t dp_device_init(chaindp_ctx *ctx, bool twin_stamp, bool dense_stamp, std::string &what)
+{
+	DpDevice &d = ctx->dp;
+	hipError_t e = hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+	if (e != hipSuccess) return e;
+	if (twin_stamp) e = (hipError_t)ctx->pool.alloc((void**)&d.twin_stamp, twin_stamp_bytes(d.cus));
+	if (e == hipSuccess && dense_stamp) e = (hipError_t)ctx->pool.alloc((void**)&d.dense_stamp, 16 * sizeof(unsigned long long));
+	if (e != hipSuccess) return e;
+	DpKernel k[CHAINDP_DP_KERNELS];
+	int n = twin_kernels(k);
+	n += units_kernels(k + n); n += dense_kernels(k + n); n += dense16_kernels(k + n); n += dense1_kernels(k + n);
+	for (int i = 0; i < n; ++i) {
+		hipFuncAttributes fa;
+		e = hipFuncGetAttributes(&fa, k[i].fn);
+		if (e == hipSuccess && fa.sharedSizeBytes != 0) e = hipErrorInvalidConfiguration;   // static LDS in front of the dynamic segment
+		if (e == hipSuccess && k[i].max_lds > 64 * 1024) e = hipFuncSetAttribute(k[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k[i].max_lds);
+		if (e != hipSuccess) { what = std::string(k[i].name) + ": "; return e; }
+	}
+	return hipSuccess;
+}
+
 extern "C" chaindp_ctx_t *chaindp_create(int device, int64_t max_anchors, int64_t max_reads)
 {
 	int n_dev = 0;
@@ -171,12 +195,14 @@ extern "C" chaindp_ctx_t *chaindp_create(int device, int64_t max_anchors, int64_
 		ctx->cmp.single_mask = ctx->pre.single_mask; ctx->cmp.emit_mask = ctx->pre.emit_mask; ctx->cmp.block_reads = ctx->pre.block_reads;
 		ctx->pre.key_range = ctx->pre.hist + 2 * 128;
 	}
-	ctx->use_quad = getenv("CHAINDP_QUAD") != nullptr;
 	ctx->deep_handover = getenv("CHAINDP_NO_DEEP_HANDOVER") == nullptr;      // diagnostic switches are read here, once per context:
 	if (const char *v = getenv("CHAINDP_TWIN_FORCE_LEFT")) ctx->twin_force_left = atoi(v) == 2 ? 2 : 1;   // never on the launch path (contexts run from several host threads)
 	if (const char *v = getenv("CHAINDP_SKETCH_MAX_BASES")) { const long long m = atoll(v); if (m >= 0 && m < ctx->sk_max_bases) ctx->sk_max_bases = m; }
+	if (const char *v = getenv("CHAINDP_TWIN_WG_PER_CU")) ctx->dp.twin_wg_per_cu = atoi(v);
+	std::string what;
+	if (e == hipSuccess) e = dp_device_init(ctx, getenv("CHAINDP_TWIN_STAMP") != nullptr, getenv("CHAINDP_DENSE_STAMP") != nullptr, what);
 	if (e != hipSuccess) {
-		g_create_error = std::string("chaindp_create: ") + hipGetErrorString(e);
+		g_create_error = std::string("chaindp_create: ") + what + hipGetErrorString(e);
 		chaindp_destroy(ctx);
 		return nullptr;
 	}
@@ -221,10 +247,9 @@ static int run_on_stream(chaindp_ctx *ctx, const chaindp_params_t *par, int64_t 
 	}
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	const Params q = to_params(par);
-	const HandoverWords hw(ctx);
 	EventSet es;
 	HIP_TRY(ctx, prof_begin(ctx, es, 3, 0, st));
-	HIP_TRY(ctx, chaindp::launch_prepass(st, q, n_reads, total, d_off, d_a, ctx->d_sumq, ctx->d_units, ctx->d_counters, ctx->pre, ctx->d_unit_aux, d_n_segs, hw.all()));
+	HIP_TRY(ctx, chaindp::launch_prepass(st, q, n_reads, total, d_off, d_a, ctx->d_sumq, ctx->d_units, ctx->d_counters, ctx->pre, ctx->d_unit_aux, d_n_segs, ctx->d_left_cnt));
 	HIP_TRY(ctx, prof_mark(ctx, es, 1, st));
 	// per-read gap-cost table for the fast variant (skipped when the table would not apply)
 	uint16_t *lut = nullptr;
@@ -243,40 +268,26 @@ static int run_on_stream(chaindp_ctx *ctx, const chaindp_params_t *par, int64_t 
 		HIP_TRY(ctx, hipMemsetAsync(ctx->d_tg, 0, (size_t)ctx->cap_anchors * 8, st));
 		ctx->epoch = 1;
 	}
-	// (the hand-over words -- counts, queue words, the route flag -- were zeroed by the prepass' first kernel)
-	Unit *const deep = ctx->deep_handover ? ctx->d_deep : nullptr;
-	if (ctx->variant == 0 && lut) {
-		// ordinary units two per wave; what that kernel hands over (and nothing else) goes through k_chain_units
-		// (first_child[] is initialised by the DP kernels themselves, per tile: no batch-wide memset)
-		// four units per wave where the whole batch has one cost table, else two per wave: both are launched, the device decides
-		Params qt = q;                          // with per-read segment counts the units' UnitAux flags say which reads are multi-segment
-		if (d_n_segs) qt.n_segs = 1;            // (the batch-wide count is not used then, as in k_chain_units)
-		if (ctx->use_quad)
-			HIP_TRY(ctx, chaindp::launch_chain_quad(st, qt, total / 2, d_a, lut, lut_stride, ctx->d_units, ctx->d_unit_aux, ctx->d_counters, ctx->pre.key_range,
-			                                        d_f, d_p, d_v, ctx->d_first_child, ctx->cmp.flags, ctx->d_left, hw.left_count(),
-			                                        hw.left_queue(), hw.route(), ctx->twin_force_left, total));
-		HIP_TRY(ctx, chaindp::launch_chain_twin(st, qt, total / 2, d_off, d_a, ctx->d_sumq, lut, lut_stride, ctx->d_units, ctx->d_counters,
-		                                        d_f, d_p, d_v, ctx->d_first_child, ctx->cmp.flags, ctx->d_left, hw.left_count(),
-		                                        ctx->twin_force_left, total, ctx->d_unit_aux, ctx->pre.key_range, hw.route(), ctx->d_twin_queue,
-		                                        ctx->twin_two_tables));
-		const int64_t left_grid = total / 2 < 32768 ? total / 2 : 32768;
-		HIP_TRY(ctx, chaindp::launch_chain(st, ctx->ring, q, left_grid, d_off, d_a, d_n_segs, ctx->d_sumq, lut, lut_stride, ctx->d_left,
-		                                   hw.left_word(), d_f, d_p, d_v, ctx->d_tg, ctx->epoch, ctx->d_first_child, ctx->cmp.flags,
-		                                   ctx->d_units, ctx->d_counters, deep, hw.deep_count(), ctx->pre.hist + CHAINDP_LONG_UNIT_CLASS, ctx->deep_eager, ctx->deep_route));
-	} else
-		HIP_TRY(ctx, chaindp::launch_chain(st, ctx->ring, q, total / 2, d_off, d_a, d_n_segs, ctx->d_sumq, lut, lut_stride, ctx->d_units,
-		                                   ctx->d_counters, d_f, d_p, d_v, ctx->d_tg, ctx->epoch, ctx->d_first_child, ctx->cmp.flags,
-		                                   nullptr, nullptr, deep, hw.deep_count(), ctx->pre.hist + CHAINDP_LONG_UNIT_CLASS, ctx->deep_eager, ctx->deep_route));
-	// units whose scans kept reaching past the ring (dense repeats): redone by k_chain_dense
-	if (deep && lut) {
-		HIP_TRY(ctx, chaindp::launch_chain_dense(st, q, total / 64 + 1, d_off, d_a, lut, lut_stride, ctx->d_deep, hw.deep_word(),
-		                                         d_f, d_p, d_v, ctx->d_first_child, ctx->cmp.flags, ctx->pre.hist + CHAINDP_LONG_UNIT_CLASS, ctx->deep_route,
-		                                         hw.dense_queue()));
-		HIP_TRY(ctx, chaindp::launch_chain_dense16(st, q, total / 64 + 1, d_off, d_a, lut, lut_stride, ctx->d_deep, hw.deep_word(),
-		                                           d_f, d_p, d_v, ctx->d_first_child, ctx->cmp.flags, ctx->pre.hist + CHAINDP_LONG_UNIT_CLASS, ctx->deep_route,
-		                                           hw.dense_queue()));
-		HIP_TRY(ctx, chaindp::launch_chain_dense1(st, q, total / 64 + 1, d_off, d_a, lut, lut_stride, ctx->d_deep, hw.deep_word(),
-		                                          ctx->pre.hist + CHAINDP_LONG_UNIT_CLASS, ctx->deep_route, hw.dense1_queues(), d_f, d_p, d_v, ctx->d_first_child, ctx->cmp.flags));
+	// (the hand-over words -- counts, queue words, the route flag -- were zeroed by the prepass' first kernel;
+	// first_child[] is initialised by the DP kernels themselves, per tile: no batch-wide memset)
+	DpBatch b;
+	b.st = st; b.par = q; b.total = total;
+	b.off = d_off; b.a = d_a; b.n_segs = d_n_segs; b.sumq = ctx->d_sumq; b.lut = lut; b.lut_stride = lut_stride;
+	b.units = ctx->d_units; b.aux = ctx->d_unit_aux; b.counters = ctx->d_counters;
+	b.f = d_f; b.p = d_p; b.v = d_v; b.first_child = ctx->d_first_child; b.flags = ctx->cmp.flags; b.tg = ctx->d_tg; b.epoch = ctx->epoch;
+	b.left = ctx->d_left; b.deep = ctx->deep_handover ? ctx->d_deep : nullptr; b.hw = HandoverWords{ctx->d_left_cnt};
+	b.key_range = ctx->pre.key_range; b.long_units = ctx->pre.hist + CHAINDP_LONG_UNIT_CLASS; b.twin_queue = ctx->d_twin_queue;
+	b.force_left = ctx->twin_force_left; b.two_tables = ctx->twin_two_tables; b.deep_eager = ctx->deep_eager; b.deep_route = ctx->deep_route;
+	// ordinary units two per wave (both layouts are launched, the device decides); what that kernel hands over, and nothing else,
+	// goes through k_chain_units
+	const bool twin = ctx->variant == 0 && lut;
+	if (twin) HIP_TRY(ctx, chaindp::launch_chain_twin(ctx->dp, b));
+	HIP_TRY(ctx, chaindp::launch_chain(b, ctx->ring, twin));
+	// units whose scans kept reaching past the ring (dense repeats): redone by the dense kernels
+	if (b.deep && lut) {
+		HIP_TRY(ctx, chaindp::launch_chain_dense(ctx->dp, b));
+		HIP_TRY(ctx, chaindp::launch_chain_dense16(ctx->dp, b));
+		HIP_TRY(ctx, chaindp::launch_chain_dense1(ctx->dp, b));
 	}
 	HIP_TRY(ctx, prof_mark(ctx, es, 2, st));
 	ctx->stats[2] = total; ctx->stats[3] = n_reads;
@@ -404,27 +415,9 @@ extern "C" int64_t chaindp_debug_leftover(chaindp_ctx_t *ctx)
 	if (!ctx || !ctx->d_left_cnt) return -1;
 	unsigned long long c = 0, cnt = 0;
 	if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
-	    hipMemcpy(&c, HandoverWords(ctx).left_word(), sizeof(c), hipMemcpyDeviceToHost) != hipSuccess ||
+	    hipMemcpy(&c, HandoverWords{ctx->d_left_cnt}.left_word(), sizeof(c), hipMemcpyDeviceToHost) != hipSuccess ||
 	    hipMemcpy(&cnt, ctx->d_counters, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess) return -1;
 	return (uint32_t)c == 0xffffffffu ? (int64_t)(uint32_t)cnt : (int64_t)(uint32_t)c;
-}
-
-// test hook (not in the public header): 1 lets k_chain_quad take the batches it can (one cost table, ordinary units), 0 (default) never
-extern "C" int chaindp_debug_set_quad(chaindp_ctx_t *ctx, int on)
-{
-	if (!ctx) return CHAINDP_ERR_ARG;
-	ctx->use_quad = on != 0;
-	return CHAINDP_OK;
-}
-
-// test hook (not in the public header): 1 if k_chain_quad took the last batch
-extern "C" int chaindp_debug_quad_took(chaindp_ctx_t *ctx)
-{
-	if (!ctx || !ctx->d_left_cnt) return -1;
-	unsigned long long r = 0;
-	if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
-	    hipMemcpy(&r, HandoverWords(ctx).route_word(), sizeof(r), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-	return (uint32_t)r == 1u;
 }
 
 // test hook (not in the public header): 1 keeps k_chain_twin on its layout with a cost table per half even where the batch has one
@@ -442,13 +435,13 @@ extern "C" int64_t chaindp_debug_twin_lds_bytes(int one_table) { return (int64_t
 extern "C" int chaindp_debug_twin_max_wg_per_cu(int samegap, int one_table) { return chaindp::twin_max_wg_per_cu(samegap != 0, one_table != 0); }
 
 // test hook (not in the public header): which layout k_chain_twin ran the last batch with -- 1 one cost table per wave, 2 one per
-// half, 0 neither (k_chain_quad took the batch, or the twin kernel declined it as a whole)
+// half, 0 neither (the twin kernel declined the batch as a whole, or did not run)
 extern "C" int chaindp_debug_twin_tables(chaindp_ctx_t *ctx)
 {
 	if (!ctx || !ctx->d_left_cnt) return -1;
 	unsigned long long r = 0;
 	if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
-	    hipMemcpy(&r, HandoverWords(ctx).route_word(), sizeof(r), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+	    hipMemcpy(&r, HandoverWords{ctx->d_left_cnt}.route_word(), sizeof(r), hipMemcpyDeviceToHost) != hipSuccess) return -1;
 	return (uint32_t)r == 2u ? 1 : (uint32_t)r == 3u ? 2 : 0;
 }
 
@@ -480,7 +473,7 @@ extern "C" int64_t chaindp_debug_deep_units(chaindp_ctx_t *ctx)
 	if (!ctx || !ctx->d_left_cnt) return -1;
 	unsigned long long c = 0;
 	if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
-	    hipMemcpy(&c, HandoverWords(ctx).deep_word(), sizeof(c), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+	    hipMemcpy(&c, HandoverWords{ctx->d_left_cnt}.deep_word(), sizeof(c), hipMemcpyDeviceToHost) != hipSuccess) return -1;
 	return (int64_t)(uint32_t)c;
 }
 

@@ -15,6 +15,7 @@ struct EventSet { hipEvent_t e[3]; int n; int slot0; };  // e[0..n): consecutive
 
 struct chaindp_ctx {
 	int device = -1;
+	chaindp::DpDevice dp;            // what the DP launchers need of the device and the process (filled by chaindp_create)
 	// every device buffer below is an entry of this pool: allocated, grown and freed through it and nowhere else
 	chaindp::DevPool pool{[](void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }, [](void *p) { return (int)hipFree(p); }};
 	hipStream_t stream = nullptr;
@@ -36,13 +37,11 @@ struct chaindp_ctx {
 	chaindp::Unit *d_units = nullptr;
 	chaindp::UnitAux *d_unit_aux = nullptr;   // per unit, beside d_units: what k_chain_twin needs to pick it up without further loads
 	chaindp::Unit *d_left = nullptr;          // units the two-per-wave kernel hands over to k_chain_units
-	unsigned long long *d_left_cnt = nullptr; // the four hand-over words: counts, queue words and the route flag (HandoverWords, below)
+	unsigned long long *d_left_cnt = nullptr; // the four hand-over words: counts, queue words and the route flag (chaindp::HandoverWords)
 	chaindp::Unit *d_deep = nullptr;          // units k_chain_units hands over to its k_chain_dense (scans that keep reaching past the ring)
 	int deep_route = 0;                   // test hook: 1 k_chain_dense, 2 k_chain_dense1 whatever the batch looks like
 	int deep_eager = 0;                   // test hook: hand over any unit with a few deep scans, whatever its length
 	bool deep_handover = true;            // CHAINDP_NO_DEEP_HANDOVER (diagnostic / A-B): every unit stays in the launch that took it
-	bool use_quad = false;                // CHAINDP_QUAD=1 / chaindp_debug_set_quad (A/B, tests): one-table batches of ordinary units four per wave
-	                                      // (k_chain_quad: correct, measured slower than k_chain_twin -- DESIGN.md section 6 -- so off by default)
 	int twin_two_tables = 0;              // chaindp_debug_set_twin_tables (tests): 1 keeps one-key batches on k_chain_twin's two-table layout
 	int twin_force_left = 0;              // CHAINDP_TWIN_FORCE_LEFT / chaindp_debug_set_twin_handover (tests): 1 k_chain_twin hands every unit
 	                                      // over untouched, 2 after its first tile (k_chain_units resumes there); the variable is read once, at chaindp_create
@@ -134,29 +133,6 @@ struct chaindp_index {
 			return CHAINDP_ERR_HIP;                                                                \
 		}                                                                                          \
 	} while (0)
-
-// The four 64-bit hand-over words of a run (chaindp_ctx::d_left_cnt), zeroed together by the prepass' first kernel:
-//   word 0  low half: units k_chain_twin / k_chain_quad handed over to k_chain_units (d_left; 0xffffffff = the twin kernel declined
-//           the batch, every unit); high half: the twin / quad kernel's queue word
-//   word 1  low half: units k_chain_units handed over to the dense kernels (d_deep)
-//   word 2  k_chain_dense1's two queues, one per half
-//   word 3  low half: the route flag, 1 = k_chain_quad took the batch, 2 / 3 = k_chain_twin with one / two cost tables; high half:
-//           the queue word of k_chain_dense / k_chain_dense16
-// Each accessor has the type the launcher that takes it declares; the *_word ones are also what the debug getters read back.
-struct HandoverWords {
-	unsigned long long *w;
-	explicit HandoverWords(const chaindp_ctx *ctx) : w(ctx->d_left_cnt) {}
-	unsigned long long *all() const { return w; }                                // launch_prepass, which zeroes the four
-	unsigned long long *left_word() const { return w; }
-	unsigned int *left_count() const { return (unsigned int*)w; }
-	unsigned int *left_queue() const { return (unsigned int*)w + 1; }
-	unsigned long long *deep_word() const { return w + 1; }
-	unsigned int *deep_count() const { return (unsigned int*)(w + 1); }
-	unsigned int *dense1_queues() const { return (unsigned int*)(w + 2); }
-	unsigned long long *route_word() const { return w + 3; }
-	unsigned int *route() const { return (unsigned int*)(w + 3); }
-	unsigned int *dense_queue() const { return (unsigned int*)(w + 3) + 1; }
-};
 
 namespace chaindp {
 

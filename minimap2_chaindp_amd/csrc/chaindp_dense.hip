@@ -46,12 +46,16 @@ namespace dense16 {
 #define DN_WAVES 16
 #define DN_ROUND 16
 #define DN_LAUNCH launch_chain_dense16
+#define DN_KERNELS dense16_kernels
+#define DN_NAME "k_chain_dense16"
 #define DN_WIDE 1
 #else
 #define DN_RING CHAINDP_DENSE_RING
 #define DN_WAVES 8                      // waves per unit
 #define DN_ROUND 8                      // chunks per round
 #define DN_LAUNCH launch_chain_dense
+#define DN_KERNELS dense_kernels
+#define DN_NAME "k_chain_dense"
 #define DN_WIDE 0
 #endif
 #define DN_CPW (DN_ROUND / DN_WAVES)    // chunks a wave evaluates per round
@@ -436,42 +440,27 @@ static size_t dense_lds_bytes(int lut_stride) { return (size_t)DN_LUT + (size_t)
 using namespace dense16;
 #endif
 
-hipError_t DN_LAUNCH(hipStream_t st, const Params &par, int64_t max_units, const int64_t *d_off, const void *d_a,
-                     const uint16_t *d_lut, int lut_stride, const Unit *d_deep, const unsigned long long *d_deep_cnt,
-                     int32_t *d_f, int32_t *d_p, int32_t *d_v, int32_t *d_first_child, uint8_t *d_flags,
-                     const unsigned int *d_long_units, int deep_route, unsigned int *d_queue)
+hipError_t DN_LAUNCH(const DpDevice &dev, const DpBatch &b)
 {
-	if (max_units <= 0 || !d_lut) return hipSuccess;
-	if (!d_queue) return hipErrorInvalidValue;
-	const size_t lds = dense_lds_bytes(lut_stride);
-	int dev = 0, cus = 256;
-	if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+	const Params &par = b.par;
+	const int64_t max_units = b.total / 64 + 1;      // a unit is handed over after its first 64-anchor tile at the earliest
+	if (!b.lut) return hipSuccess;
+	hipStream_t st = b.st;
+	const size_t lds = dense_lds_bytes(b.lut_stride);
 	// the count is only known on the device: as many workgroups as the chip holds at this LDS size, each taking units in turn
 	int64_t per_cu = (int64_t)(160 * 1024 / lds);
 	if (per_cu > 8) per_cu = 8;
 	if (per_cu < 1) per_cu = 1;
-	int64_t blocks = (int64_t)cus * per_cu;
+	int64_t blocks = (int64_t)dev.cus * per_cu;
 	if (DN_WIDE && blocks > (int64_t)CHAINDP_DENSE16_MAX_UNITS) blocks = CHAINDP_DENSE16_MAX_UNITS;   // (it only ever takes that many units: fewer workgroups to start and end for nothing)
 	if (blocks > max_units) blocks = max_units;
-	const void *fn = par.max_dist_y >= par.max_dist_x ? (const void*)k_chain_dense<true> : (const void*)k_chain_dense<false>;
-	{
-		const hipError_t e = check_no_static_lds(fn);        // LDS is addressed by raw byte offsets from 0
-		if (e != hipSuccess) return e;
-	}
-	if (lds > 64 * 1024) {
-		const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-		if (e != hipSuccess) return e;
-	}
 	DenseArgs g;
-	g.par = par; g.off = d_off; g.a = (const ulonglong2*)d_a; g.lut = d_lut; g.lut_stride = lut_stride;
-	g.units = d_deep; g.count = d_deep_cnt; g.f = d_f; g.p = d_p; g.v = d_v; g.first_child = d_first_child; g.flags = d_flags;
-	g.long_units = d_long_units; g.route = deep_route; g.queue = d_queue;
+	g.par = par; g.off = b.off; g.a = (const ulonglong2*)b.a; g.lut = b.lut; g.lut_stride = b.lut_stride;
+	g.units = b.deep; g.count = b.hw.deep_word(); g.f = b.f; g.p = b.p; g.v = b.v; g.first_child = b.first_child; g.flags = b.flags;
+	g.long_units = b.long_units; g.route = b.deep_route; g.queue = b.hw.dense_queue();
 	g.stamp = nullptr;
 #ifdef CHAINDP_DENSE_STAMPS
-	static unsigned long long *d_stamp = nullptr;
-	static const bool stamp = getenv("CHAINDP_DENSE_STAMP") != nullptr;
-	if (stamp && !d_stamp && hipMalloc((void**)&d_stamp, 16 * 8) != hipSuccess) d_stamp = nullptr;
-	if (stamp && d_stamp) { (void)hipMemsetAsync(d_stamp, 0, 16 * 8, st); g.stamp = d_stamp; }
+	if (dev.dense_stamp) { (void)hipMemsetAsync(dev.dense_stamp, 0, 16 * 8, st); g.stamp = dev.dense_stamp; }
 #endif
 	if (par.max_dist_y >= par.max_dist_x) hipLaunchKernelGGL(k_chain_dense<true>, dim3((unsigned)blocks), dim3(64 * DN_WAVES), lds, st, g);
 	else hipLaunchKernelGGL(k_chain_dense<false>, dim3((unsigned)blocks), dim3(64 * DN_WAVES), lds, st, g);
@@ -487,6 +476,14 @@ hipError_t DN_LAUNCH(hipStream_t st, const Params &par, int64_t max_units, const
 	}
 #endif
 	return hipGetLastError();
+}
+
+// the most LDS a launch asks for: the table at its longest
+int DN_KERNELS(DpKernel *out)
+{
+	out[0] = {(const void*)k_chain_dense<true>, DN_NAME "<samegap>", dense_lds_bytes(CHAINDP_LUT_MAX_STRIDE)};
+	out[1] = {(const void*)k_chain_dense<false>, DN_NAME, dense_lds_bytes(CHAINDP_LUT_MAX_STRIDE)};
+	return 2;
 }
 
 } // namespace chaindp

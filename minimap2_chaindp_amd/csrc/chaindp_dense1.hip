@@ -277,37 +277,40 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, D1_WAVES_
 	}
 }
 
-hipError_t launch_chain_dense1(hipStream_t st, const Params &par, int64_t max_units, const int64_t *d_off, const void *d_a,
-                               const uint16_t *d_lut, int lut_stride, const Unit *d_deep, const unsigned long long *d_deep_cnt,
-                               const unsigned int *d_long_units, int deep_route, unsigned int *d_queues,
-                               int32_t *d_f, int32_t *d_p, int32_t *d_v, int32_t *d_first_child, uint8_t *d_flags)
+static size_t dense1_lds_bytes(uint32_t bm_bytes, int lut_stride) { return (size_t)D1_BM + bm_bytes + 256u + (size_t)lut_stride * 2; }
+
+hipError_t launch_chain_dense1(const DpDevice &dev, const DpBatch &b)
 {
-	if (max_units <= 0 || !d_lut) return hipSuccess;
-	int dev = 0, cus = 256;
-	if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-	const void *fn = par.max_dist_y >= par.max_dist_x ? (const void*)k_chain_dense1<true> : (const void*)k_chain_dense1<false>;
-	{
-		const hipError_t e = check_no_static_lds(fn);        // LDS is addressed by raw byte offsets from 0
-		if (e != hipSuccess) return e;
-	}
+	const Params &par = b.par;
+	const int64_t max_units = b.total / 64 + 1;      // a unit is handed over after its first 64-anchor tile at the earliest
+	if (!b.lut) return hipSuccess;
+	hipStream_t st = b.st;
 	Dense1Args g;
-	g.par = par; g.off = d_off; g.a = (const ulonglong2*)d_a; g.lut = d_lut; g.lut_stride = lut_stride;
-	g.units = d_deep; g.count = d_deep_cnt; g.long_units = d_long_units; g.route = deep_route; g.f = d_f; g.p = d_p; g.v = d_v; g.first_child = d_first_child; g.flags = d_flags;
+	g.par = par; g.off = b.off; g.a = (const ulonglong2*)b.a; g.lut = b.lut; g.lut_stride = b.lut_stride;
+	g.units = b.deep; g.count = b.hw.deep_word(); g.long_units = b.long_units; g.route = b.deep_route; g.f = b.f; g.p = b.p; g.v = b.v; g.first_child = b.first_child; g.flags = b.flags;
 	// two launches: units of up to 32 K anchors with a 4 KB bitmap (most waves per CU), the longer ones with 8 KB; the count is
 	// only known on the device, so each launch has as many waves as the chip holds at its LDS size, taking units in turn
 	const int caps[2] = {CHAINDP_DENSE_BITCAP / 2, CHAINDP_DENSE_BITCAP};
 	for (int q = 0; q < 2; ++q) {
-		g.min_len = q ? caps[q - 1] : 0; g.max_len = caps[q]; g.bm_bytes = (uint32_t)caps[q] / 8u; g.queue = d_queues + q;
-		const size_t lds = (size_t)D1_BM + g.bm_bytes + 256u + (size_t)lut_stride * 2;
+		g.min_len = q ? caps[q - 1] : 0; g.max_len = caps[q]; g.bm_bytes = (uint32_t)caps[q] / 8u; g.queue = b.hw.dense1_queues() + q;
+		const size_t lds = dense1_lds_bytes(g.bm_bytes, b.lut_stride);
 		int64_t per_cu = (int64_t)(160 * 1024 / lds);
 		if (per_cu > 24) per_cu = 24;
 		if (per_cu < 1) per_cu = 1;
-		int64_t blocks = (int64_t)cus * per_cu;
+		int64_t blocks = (int64_t)dev.cus * per_cu;
 		if (blocks > max_units) blocks = max_units;
 		if (par.max_dist_y >= par.max_dist_x) hipLaunchKernelGGL(k_chain_dense1<true>, dim3((unsigned)blocks), dim3(64), lds, st, g);
 		else hipLaunchKernelGGL(k_chain_dense1<false>, dim3((unsigned)blocks), dim3(64), lds, st, g);
 	}
 	return hipGetLastError();
+}
+
+int dense1_kernels(DpKernel *out)
+{
+	const size_t lds = dense1_lds_bytes(CHAINDP_DENSE_BITCAP / 8u, CHAINDP_LUT_MAX_STRIDE);   // the longer bitmap, the table at its longest
+	out[0] = {(const void*)k_chain_dense1<true>, "k_chain_dense1<samegap>", lds};
+	out[1] = {(const void*)k_chain_dense1<false>, "k_chain_dense1", lds};
+	return 2;
 }
 
 } // namespace chaindp

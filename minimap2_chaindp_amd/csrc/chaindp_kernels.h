@@ -41,15 +41,15 @@ struct PrepassScratch {
 	Unit *units_tmp;                 // units in anchor order, before the longest-first scatter
 	unsigned int *hist;              // 2 x 128: length-class histogram / bases, cursors
 	int2 *block_reads;               // per 1024-anchor block: reads of its first and last anchor (also used by the compaction)
-	unsigned int *key_range;         // [0] smallest, [1] largest UnitAux::lutkey among the units k_chain_twin / k_chain_quad may take
+	unsigned int *key_range;         // [0] smallest, [1] largest UnitAux::lutkey among the units k_chain_twin may take
 };
 size_t prepass_scratch_bytes(int64_t max_anchors, size_t *mask_bytes, size_t *blocks_bytes);
 
 // counters[0] = units emitted (low 32 bits) | singleton anchors resolved by the prepass (high 32 bits)
+// d_left_cnt: the four hand-over words (HandoverWords, below), zeroed with the batch's other accumulators
 hipError_t launch_prepass(hipStream_t st, const Params &par, int64_t n_reads, int64_t total, const int64_t *d_off, const void *d_a,
                           unsigned long long *d_sumq, Unit *d_units, unsigned long long *d_counters, PrepassScratch sc,
-                          UnitAux *d_unit_aux = nullptr, const int32_t *d_n_segs = nullptr,
-                          unsigned long long *d_left_cnt = nullptr);   // d_left_cnt: four hand-over words, zeroed with the batch's other accumulators
+                          UnitAux *d_unit_aux, const int32_t *d_n_segs, unsigned long long *d_left_cnt);
 // f, p, v, flags[] of the batch's singletons (the prepass only marks them; the compaction reads the marks)
 hipError_t launch_fill_singles(hipStream_t st, const Params &par, int64_t total, const void *d_a, PrepassScratch sc,
                                int32_t *d_f, int32_t *d_p, int32_t *d_v, uint8_t *d_flags);
@@ -57,67 +57,111 @@ hipError_t launch_fill_singles(hipStream_t st, const Params &par, int64_t total,
 // Per-read gap-cost table (uint16), lut_stride entries per read (multiple of 8); usable while
 // bw <= CHAINDP_LUT_MAX_BW.  d_lut == nullptr makes every unit take the general (f64) variant.
 #define CHAINDP_LUT_MAX_BW 4095
+#define CHAINDP_LUT_MAX_STRIDE ((CHAINDP_LUT_MAX_BW + 1 + 7) & ~7)
 hipError_t launch_lut(hipStream_t st, const Params &par, int64_t n_reads, const int64_t *d_off,
                       unsigned long long *d_sumq, int lut_stride, uint16_t *d_lut);
 size_t chain_lds_bytes(int ring, int lut_stride);
 
-hipError_t launch_chain(hipStream_t st, int ring, const Params &par, int64_t max_units, const int64_t *d_off, const void *d_a,
-                        const int32_t *d_n_segs, const unsigned long long *d_sumq, const uint16_t *d_lut, int lut_stride,
-                        const Unit *d_units, const unsigned long long *d_counters,
-                        int32_t *d_f, int32_t *d_p, int32_t *d_v, unsigned long long *d_tg, uint32_t epoch, int32_t *d_first_child, uint8_t *d_flags,
-                        const Unit *d_units_all = nullptr, const unsigned long long *d_counters_all = nullptr,
-                        Unit *d_deep = nullptr, unsigned int *d_deep_cnt = nullptr, const unsigned int *d_long_units = nullptr,
-                        int deep_eager = 0,    // tests: hand over any unit with a few deep scans
-                        int deep_route = 0);   // 0: the batch decides which dense kernel runs; 1: k_chain_dense; 2: k_chain_dense1; 3: k_chain_dense16 (tests)
-// *d_long_units: units of CHAINDP_LONG_UNIT anchors and more in the batch (PrepassScratch::hist + CHAINDP_LONG_UNIT_CLASS, valid
-// after launch_prepass); above CHAINDP_DENSE_MAX_LONG of them nothing is handed over
+// The four 64-bit hand-over words of a run, zeroed together by the prepass' first kernel:
+//   word 0  low half: units k_chain_twin handed over to k_chain_units (DpBatch::left; 0xffffffff = the twin kernel declined the
+//           batch, every unit); high half: unused
+//   word 1  low half: units k_chain_units handed over to the dense kernels (DpBatch::deep)
+//   word 2  k_chain_dense1's two queues, one per half
+//   word 3  low half: the route flag, 2 / 3 = k_chain_twin took the batch with one / two cost tables (1 is retired: the kernel with
+//           four units per wave wrote it); high half: the queue word of k_chain_dense / k_chain_dense16
+// Each accessor has the type the kernel argument it fills has; the *_word ones are also what the debug getters read back.
+struct HandoverWords {
+	unsigned long long *w;
+	unsigned long long *left_word() const { return w; }
+	unsigned int *left_count() const { return (unsigned int*)w; }
+	unsigned long long *deep_word() const { return w + 1; }
+	unsigned int *deep_count() const { return (unsigned int*)(w + 1); }
+	unsigned int *dense1_queues() const { return (unsigned int*)(w + 2); }
+	unsigned long long *route_word() const { return w + 3; }
+	unsigned int *route() const { return (unsigned int*)(w + 3); }
+	unsigned int *dense_queue() const { return (unsigned int*)(w + 3) + 1; }
+};
+
+// What the DP kernels see of one batch.  The host fills it once per run, after the prepass and the cost tables; every launcher
+// below reads what its kernel takes from it.
+struct DpBatch {
+	hipStream_t st;
+	Params par;
+	int64_t total;                       // anchors
+	const int64_t *off;
+	const void *a;
+	const int32_t *n_segs;               // per read, or nullptr: par.n_segs for all
+	const unsigned long long *sumq;
+	const uint16_t *lut;                 // nullptr: no tables, every unit takes the general variant
+	int lut_stride;
+	const Unit *units;                   // the prepass' list, longest first, counters[0] of them
+	const UnitAux *aux;
+	const unsigned long long *counters;
+	int32_t *f, *p, *v, *first_child;
+	uint8_t *flags;
+	unsigned long long *tg;              // deep-path marks of k_chain_units, tagged with epoch
+	uint32_t epoch;
+	Unit *left;                          // units k_chain_twin hands over to k_chain_units
+	Unit *deep;                          // units k_chain_units hands over to the dense kernels; nullptr: none are handed over
+	HandoverWords hw;
+	const unsigned int *key_range;       // PrepassScratch::key_range
+	const unsigned int *long_units;      // units of CHAINDP_LONG_UNIT anchors and more (PrepassScratch::hist + CHAINDP_LONG_UNIT_CLASS);
+	                                     // above CHAINDP_DENSE_MAX_LONG of them nothing is handed over
+	unsigned int *twin_queue;            // 8 x 64 words: k_chain_twin's grab counters
+	// test switches
+	int force_left;                      // k_chain_twin: 1 hands every unit over untouched, 2 after its first tile
+	int two_tables;                      // k_chain_twin: keep every batch on the two-table layout
+	int deep_eager;                      // k_chain_units: hand over any unit with a few deep scans
+	int deep_route;                      // 0: the batch decides which dense kernel runs; 1: k_chain_dense; 2: k_chain_dense1; 3: k_chain_dense16
+};
+
+// What the launchers need to know of the device and the process: filled by chaindp_create, read-only afterwards
+struct DpDevice {
+	int cus = 256;
+	int twin_wg_per_cu = 0;                      // CHAINDP_TWIN_WG_PER_CU (tuning): fewer workgroups of k_chain_twin per CU; 0 = what fits
+	// diagnostic runs (they synchronise after the launch and print): allocated only when their switch is set
+	unsigned long long *twin_stamp = nullptr;    // CHAINDP_TWIN_STAMP: 12 words per workgroup of k_chain_twin's largest grid
+	unsigned long long *dense_stamp = nullptr;   // CHAINDP_DENSE_STAMP: 16 words
+};
+size_t twin_stamp_bytes(int cus);
+
+// A DP kernel instantiation.  All of them address LDS by raw byte offsets from 0, so none may have static LDS in front of its
+// dynamic segment; max_lds is the most dynamic LDS a launch can ask it for.  chaindp_create checks the one and provides for the
+// other, once per context; every *_kernels() below lists the instantiations of one source file into out[] and returns their number.
+struct DpKernel { const void *fn; const char *name; size_t max_lds; };
+#define CHAINDP_DP_KERNELS 13
+int twin_kernels(DpKernel *out);      // 4
+int units_kernels(DpKernel *out);     // 3
+int dense_kernels(DpKernel *out);     // 2
+int dense16_kernels(DpKernel *out);   // 2
+int dense1_kernels(DpKernel *out);    // 2
+
+// k_chain_units (chaindp_kernels.hip), one unit per wave: the prepass' whole unit list, or (leftovers) what k_chain_twin handed
+// over -- b.left, or the whole list again where that kernel declined the batch.  Units whose scans keep reaching past the ring
+// (dense repeats) are appended to b.deep (when given) and redone by the dense kernels.
+hipError_t launch_chain(const DpBatch &b, int ring, bool leftovers);
 #define CHAINDP_LONG_UNIT_CLASS 65      // hist[c] after k_unit_bases = units in length classes above c; class 65 ends at 8191 anchors
 #define CHAINDP_DENSE_MAX_LONG 4096u
-// Units whose scans keep reaching past the ring (dense repeats) are appended to d_deep / *d_deep_cnt by the launch above (when
-// given) and redone by k_chain_dense (chaindp_dense.hip): a workgroup of four waves per unit, marks as one bit per distance in
-// LDS.  The low 32 bits of *d_deep_cnt are the count.  Only units of at most CHAINDP_DENSE_BITCAP anchors are handed over (the
-// bitmap covers that many distances), and only while 32-bit differences are exact over a ring of CHAINDP_DENSE_RING anchors.
+// k_chain_dense (chaindp_dense.hip): a workgroup of eight waves per unit of b.deep, marks as one bit per distance in LDS.  Only units
+// of at most CHAINDP_DENSE_BITCAP anchors are handed over (the bitmap covers that many distances), and only while 32-bit differences
+// are exact over a ring of CHAINDP_DENSE_RING anchors.
 #define CHAINDP_DENSE_BITCAP 65536
 #define CHAINDP_DENSE_RING 512
 #define CHAINDP_DENSE_UNITS 2048u      // units handed over per batch (about two rounds of workgroups on the chip)
-hipError_t launch_chain_dense(hipStream_t st, const Params &par, int64_t max_units, const int64_t *d_off, const void *d_a,
-                              const uint16_t *d_lut, int lut_stride, const Unit *d_deep, const unsigned long long *d_deep_cnt,
-                              int32_t *d_f, int32_t *d_p, int32_t *d_v, int32_t *d_first_child, uint8_t *d_flags,
-                              const unsigned int *d_long_units, int deep_route, unsigned int *d_queue);   // d_queue: one zeroed word (the unit counter)
+hipError_t launch_chain_dense(const DpDevice &dev, const DpBatch &b);
 // the same with sixteen waves per unit (chaindp_dense.hip built with -DDN_VARIANT16): the device sends a short tail there
-hipError_t launch_chain_dense16(hipStream_t st, const Params &par, int64_t max_units, const int64_t *d_off, const void *d_a,
-                              const uint16_t *d_lut, int lut_stride, const Unit *d_deep, const unsigned long long *d_deep_cnt,
-                              int32_t *d_f, int32_t *d_p, int32_t *d_v, int32_t *d_first_child, uint8_t *d_flags,
-                              const unsigned int *d_long_units, int deep_route, unsigned int *d_queue);   // d_queue: one zeroed word (the unit counter)
+hipError_t launch_chain_dense16(const DpDevice &dev, const DpBatch &b);
 // ... or, when the batch is dense all over, by k_chain_dense1 (chaindp_dense1.hip): one wave per unit, many per CU, the same bit
-// marks, deep chunks four at a time.  Both are launched; the device decides which one has work (dense_all(), chaindp_fast.h).
-hipError_t launch_chain_dense1(hipStream_t st, const Params &par, int64_t max_units, const int64_t *d_off, const void *d_a,
-                               const uint16_t *d_lut, int lut_stride, const Unit *d_deep, const unsigned long long *d_deep_cnt,
-                               const unsigned int *d_long_units, int deep_route, unsigned int *d_queues,   // d_queues: two zeroed words
-                               int32_t *d_f, int32_t *d_p, int32_t *d_v, int32_t *d_first_child, uint8_t *d_flags);
+// marks, deep chunks four at a time.  All three are launched; the device decides which one has work (dense_all(), chaindp_fast.h).
+hipError_t launch_chain_dense1(const DpDevice &dev, const DpBatch &b);
 
 // Two units per wave, 32 lanes each (chaindp_twin.hip): takes the ordinary units, appends the others (general-variant reads,
-// scans that reach beyond 64 predecessors) to d_left / *d_left_cnt (low 32 bits = count), which launch_chain then runs.  Two LDS
-// layouts, both launched: one cost table per wave (32 workgroups per CU) for batches whose units share one table key (d_key_range),
-// else one per half (24 per CU).  *d_route (zeroed with the batch): 1 k_chain_quad took the batch, 2 the one-table layout, 3 the
-// two-table layout.  two_tables != 0 (tests) keeps every batch on the two-table layout.
-hipError_t launch_chain_twin(hipStream_t st, const Params &par, int64_t max_units, const int64_t *d_off, const void *d_a,
-                             const unsigned long long *d_sumq, const uint16_t *d_lut, int lut_stride, const Unit *d_units,
-                             const unsigned long long *d_counters, int32_t *d_f, int32_t *d_p, int32_t *d_v,
-                             int32_t *d_first_child, uint8_t *d_flags, Unit *d_left, unsigned int *d_left_cnt, int force_left, int64_t total,
-                             const UnitAux *d_unit_aux, const unsigned int *d_key_range, unsigned int *d_route,
-                             unsigned int *d_queue /* 8 x 64 words: the grab counters */, int two_tables);
+// scans that reach beyond 64 predecessors) to b.left, which launch_chain then runs.  Two LDS layouts, both launched: one cost table
+// per wave (32 workgroups per CU) for batches whose units share one table key (b.key_range), else one per half (24 per CU); the
+// route flag says which one took the batch.
+hipError_t launch_chain_twin(const DpDevice &dev, const DpBatch &b);
 size_t twin_lds_bytes(bool one_table);
 int twin_max_wg_per_cu(bool samegap, bool one_table);
-
-// Four units per wave, 16 lanes each, two predecessors per lane (chaindp_quad.hip): takes a batch of ordinary units whose reads all
-// have the same cost table (key_range: PrepassScratch::key_range) and says so in *d_route; otherwise it leaves the batch to
-// launch_chain_twin, which is launched behind it and returns at once when *d_route is set.  Same hand-over list.
-hipError_t launch_chain_quad(hipStream_t st, const Params &par, int64_t max_units, const void *d_a, const uint16_t *d_lut, int lut_stride,
-                             const Unit *d_units, const UnitAux *d_unit_aux, const unsigned long long *d_counters, const unsigned int *d_key_range,
-                             int32_t *d_f, int32_t *d_p, int32_t *d_v, int32_t *d_first_child, uint8_t *d_flags, Unit *d_left,
-                             unsigned int *d_left_cnt, unsigned int *d_queue, unsigned int *d_route, int force_left, int64_t total);
-size_t quad_lds_bytes();
 
 // exclusive scan of n uint64 items in place (d_tile_tmp: ceil(n/1024)+1 words), total to *d_total
 hipError_t launch_scan_u64(hipStream_t st, int64_t n, unsigned long long *d_data, unsigned long long *d_tile_tmp,
@@ -293,10 +337,6 @@ hipError_t launch_scatter_seeds(hipStream_t st, int64_t n_reads, const int64_t *
 // rounds bytes up to 16: both buffers must have that much room
 hipError_t launch_copy_out(hipStream_t st, void *h_dst, const void *d_src, size_t bytes, int blocks);
 hipError_t launch_scatter_words(hipStream_t st, int64_t n_reads, const int64_t *d_woff, void *const *d_dst, const void *d_words);
-
-// The DP kernels address LDS by raw byte offsets from 0, so none of them may have static LDS in front of its dynamic segment.
-// Checked once per kernel (the answer is a property of the code object), not once per launch.
-hipError_t check_no_static_lds(const void *fn);
 
 } // namespace chaindp
 #endif

@@ -21,9 +21,6 @@
 //                   predecessors older than the ring are read back from HBM/L2 (the "deep" path).
 //   Integer arithmetic only, except the reference's own f32 divide and (int)(dd * .01 * avg_qspan) in f64.
 #include <hip/hip_runtime.h>
-#include <mutex>
-#include <utility>
-#include <vector>
 #include <stdint.h>
 #include <limits.h>
 #include "chaindp_kernels.h"
@@ -298,7 +295,7 @@ __device__ __forceinline__ void run_unit(const UnitCtx &c, int64_t room)
 // run_unit<RING, true> computes, with the per-anchor instruction count cut to the bone (the kernel is bound by
 // VALU and SALU issue, not by memory):
 //   * LDS is addressed with raw byte addresses (the kernel has no static LDS, so the dynamic segment starts at 0;
-//     launch_chain checks that), which lets constant offsets fold into the DS instructions;
+//     chaindp_create checks that), which lets constant offsets fold into the DS instructions;
 //   * the ring entry holds x.lo+1, qpos+1, f and 4*p: subtracting it from the raw x_i, q_i gives dr-1 and dq-1,
 //     so the range tests "1 <= d <= max" become single unsigned compares, |dr-dq| is unchanged, and
 //     min(dq,dr,span) + f - cost = min3(dq-1,dr-1,span-1) + f + (1-cost); 4*p is the byte offset of the mark to write;
@@ -647,50 +644,37 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 
 // ---------------------------------------------------------------- launchers
 
-hipError_t check_no_static_lds(const void *fn)
-{
-	static std::mutex mu;
-	static std::vector<std::pair<const void*, hipError_t>> seen;
-	std::lock_guard<std::mutex> lk(mu);
-	for (const auto &kv : seen) if (kv.first == fn) return kv.second;
-	hipFuncAttributes fa;
-	hipError_t e = hipFuncGetAttributes(&fa, fn);
-	if (e != hipSuccess) return e;                                 // (not cached: a failed query is tried again)
-	e = fa.sharedSizeBytes != 0 ? hipErrorInvalidConfiguration : hipSuccess;
-	seen.emplace_back(fn, e);
-	return e;
-}
-
 size_t chain_lds_bytes(int ring, int lut_stride)
 {
 	return (size_t)ring * 32 + 16 + (size_t)lut_stride * 2;
 }
-hipError_t launch_chain(hipStream_t st, int ring, const Params &par, int64_t max_units, const int64_t *d_off, const void *d_a,
-                        const int32_t *d_n_segs, const unsigned long long *d_sumq, const uint16_t *d_lut, int lut_stride,
-                        const Unit *d_units, const unsigned long long *d_counters,
-                        int32_t *d_f, int32_t *d_p, int32_t *d_v, unsigned long long *d_tg, uint32_t epoch, int32_t *d_first_child, uint8_t *d_flags,
-                        const Unit *d_units_all, const unsigned long long *d_counters_all, Unit *d_deep, unsigned int *d_deep_cnt,
-                        const unsigned int *d_long_units, int deep_eager, int deep_route)
+hipError_t launch_chain(const DpBatch &b, int ring, bool leftovers)
 {
-	if (max_units <= 0) return hipSuccess;
 	// The number of units is only known on the device (counters[0]); the grid is sized for the upper
 	// bound and blocks beyond the count exit at once, so no host round trip sits between the kernels.
-	int64_t blocks = max_units;
-	const int64_t cap = 256LL * 32 * 16;
+	int64_t blocks = b.total / 2;
+	const int64_t cap = leftovers ? 32768 : 256LL * 32 * 16;      // (what k_chain_twin hands over is a small part of the batch)
 	if (blocks > cap) blocks = cap;
-	const ulonglong2 *aa = (const ulonglong2*)d_a;
-	const size_t lds = chain_lds_bytes(ring, d_lut ? lut_stride : 0);
-	{
-		const void *fn = ring == 128 ? (const void*)k_chain_units<128> : ring == 512 ? (const void*)k_chain_units<512> : (const void*)k_chain_units<256>;
-		const hipError_t e = check_no_static_lds(fn);        // LDS is addressed by raw byte offsets from 0
-		if (e != hipSuccess) return e;
-	}
-	switch (ring) {
-	case 128: hipLaunchKernelGGL(k_chain_units<128>, dim3((unsigned)blocks), dim3(64), lds, st, par, d_off, aa, d_n_segs, d_sumq, d_lut, lut_stride, d_units, d_counters, d_f, d_p, d_v, d_tg, epoch, d_first_child, d_flags, d_units_all, d_counters_all, d_deep, d_deep_cnt, d_long_units, deep_eager, deep_route); break;
-	case 512: hipLaunchKernelGGL(k_chain_units<512>, dim3((unsigned)blocks), dim3(64), lds, st, par, d_off, aa, d_n_segs, d_sumq, d_lut, lut_stride, d_units, d_counters, d_f, d_p, d_v, d_tg, epoch, d_first_child, d_flags, d_units_all, d_counters_all, d_deep, d_deep_cnt, d_long_units, deep_eager, deep_route); break;
-	default:  hipLaunchKernelGGL(k_chain_units<256>, dim3((unsigned)blocks), dim3(64), lds, st, par, d_off, aa, d_n_segs, d_sumq, d_lut, lut_stride, d_units, d_counters, d_f, d_p, d_v, d_tg, epoch, d_first_child, d_flags, d_units_all, d_counters_all, d_deep, d_deep_cnt, d_long_units, deep_eager, deep_route); break;
-	}
+	if (blocks <= 0) return hipSuccess;
+	const size_t lds = chain_lds_bytes(ring, b.lut ? b.lut_stride : 0);
+	auto kernel = k_chain_units<128>;
+	if (ring == 512) kernel = k_chain_units<512>;
+	else if (ring != 128) kernel = k_chain_units<256>;
+	// the leftover list's count is the hand-over word; all ones there send the kernel to the whole list (units_all, counters_all)
+	hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), lds, b.st, b.par, b.off, (const ulonglong2*)b.a, b.n_segs, b.sumq, b.lut, b.lut_stride,
+	                   leftovers ? (const Unit*)b.left : b.units, leftovers ? (const unsigned long long*)b.hw.left_word() : b.counters,
+	                   b.f, b.p, b.v, b.tg, b.epoch, b.first_child, b.flags,
+	                   leftovers ? b.units : (const Unit*)nullptr, leftovers ? b.counters : (const unsigned long long*)nullptr,
+	                   b.deep, b.hw.deep_count(), b.long_units, b.deep_eager, b.deep_route);
 	return hipGetLastError();
+}
+
+int units_kernels(DpKernel *out)
+{
+	out[0] = {(const void*)k_chain_units<128>, "k_chain_units<128>", chain_lds_bytes(128, CHAINDP_LUT_MAX_STRIDE)};
+	out[1] = {(const void*)k_chain_units<256>, "k_chain_units<256>", chain_lds_bytes(256, CHAINDP_LUT_MAX_STRIDE)};
+	out[2] = {(const void*)k_chain_units<512>, "k_chain_units<512>", chain_lds_bytes(512, CHAINDP_LUT_MAX_STRIDE)};
+	return 3;
 }
 
 } // namespace chaindp

@@ -1,5 +1,5 @@
-// chaindp_lanes.h -- what the part-wave DP kernels (chaindp_twin.hip: two units per wave; chaindp_quad.hip: four) share: raw LDS
-// access by byte address, loads through the scalar cache, lane masks straight from vector compares.  gfx950 only.
+// chaindp_lanes.h -- what the part-wave DP kernel (chaindp_twin.hip: two units per wave) is written with, and the prepass borrows: raw
+// LDS access by byte address, loads through the scalar cache, lane masks straight from vector compares.  gfx950 only.
 #ifndef CHAINDP_LANES_H
 #define CHAINDP_LANES_H
 
@@ -53,11 +53,9 @@ __device__ __forceinline__ tw_u32x2 tw_ld64(uint32_t a) { return *TW_LDS(const t
 __device__ __forceinline__ int tw_ld32(uint32_t a) { return *TW_LDS(const int, a); }
 __device__ __forceinline__ int tw_ld_i8(uint32_t a) { return (int)*TW_LDS(const signed char, a); }
 __device__ __forceinline__ int tw_ld_u8(uint32_t a) { return (int)*TW_LDS(const unsigned char, a); }
-__device__ __forceinline__ tw_u32x4 tw_ld128(uint32_t a) { return *TW_LDS(const tw_u32x4, a); }
 __device__ __forceinline__ void tw_st64(uint32_t a, uint32_t x, uint32_t y) { tw_u32x2 t; t.x = x; t.y = y; *TW_LDS(tw_u32x2, a) = t; }
 __device__ __forceinline__ void tw_st32(uint32_t a, int v) { *TW_LDS(int, a) = v; }
 __device__ __forceinline__ void tw_st8(uint32_t a, int v) { *TW_LDS(signed char, a) = (signed char)v; }
-__device__ __forceinline__ void tw_st128(uint32_t a, uint32_t x, uint32_t y, uint32_t z, uint32_t w) { tw_u32x4 t; t.x = x; t.y = y; t.z = z; t.w = w; *TW_LDS(tw_u32x4, a) = t; }
 
 // keeps a value in a vector register: the compiler would otherwise hold wave-uniform values in SGPRs and feed them
 // to VALU instructions as scalar operands, which halves their issue rate

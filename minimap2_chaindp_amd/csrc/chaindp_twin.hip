@@ -225,7 +225,7 @@ struct TwinArgs {
 	unsigned int *left_cnt;
 	unsigned int *queue;              // eight grab counters, 64 words apart (the halves' first grabs are dealt statically: they start behind them)
 	const unsigned int *key_range;    // [0] min, [1] max of the units' table keys (prepass)
-	unsigned int *route;              // 1: k_chain_quad took the batch; 2: the one-table layout did; 3: the two-table layout did
+	unsigned int *route;              // 2: the one-table layout took the batch; 3: the two-table layout did (1: retired, nothing writes it)
 	int two_tables;                   // test switch: 1 keeps a one-key batch on the two-table layout
 	int force_left;                   // test switch: 1 hand every unit over untouched, 2 hand every unit over after its first tile (resumed there)
 	int64_t total;                    // anchors of the batch
@@ -319,8 +319,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TwWaves<SAME
 	if (!SAMEGAP) TW_VREG(c_dqoff);
 	TW_VREG(c_min); TW_VREG(c_bwl); TW_VREG(c_cbwl);
 
-	// (uniform) which kernel takes the batch: k_chain_quad has written 1 before this kernel starts; the one-table layout takes
-	// batches whose units share one table key and writes 2, which the two-table layout, launched behind it, then finds
+	// (uniform) which layout takes the batch: the one-table layout takes batches whose units share one table key and writes 2, which
+	// the two-table layout, launched behind it, then finds.  (route == 1u: a retired value, written by the kernel with four units per
+	// wave that was launched in front of this one; nothing writes it any more.  The compare stays until a change that measures takes
+	// it out: this kernel sits at its register edge.)
 	const uint32_t route = *g.route;
 	if (ONE_LUT ? route == 1u || g.key_range[0] != g.key_range[1] || g.two_tables : route == 1u || route == 2u) return;
 	const uint32_t n_units = (uint32_t)g.counters[0];                // (32 bits: one scalar register through the pass loops)
@@ -993,43 +995,39 @@ int twin_max_wg_per_cu(bool samegap, bool one_table)
 	return 4 * waves < lds_wg ? 4 * waves : lds_wg;
 }
 
-// one launch of the layout ONE_LUT (the kernel returns at once when the batch is not for it)
-template <bool ONE_LUT>
-static hipError_t launch_twin_layout(hipStream_t st, TwinArgs g, int64_t max_units, int cus, unsigned int *d_queue)
+// the grid of a launch: persistent waves, as many as the chip holds at the layout's occupancy (LDS, and TwWaves per SIMD for the
+// registers; wg_per_cu, CHAINDP_TWIN_WG_PER_CU, lowers it), each half taking units from a queue
+static int64_t twin_blocks(int64_t max_units, int cus, int max_wg, int wg_per_cu)
 {
-	// persistent waves: as many as the chip holds at the layout's occupancy (LDS, and TwWaves per SIMD for the registers), each half
-	// taking units from a queue.  CHAINDP_TWIN_WG_PER_CU lowers it (tuning).
-	const bool samegap = g.par.max_dist_y >= g.par.max_dist_x;
-	const int max_wg = twin_max_wg_per_cu(samegap, ONE_LUT);
 	int64_t blocks = (max_units + 2 * TW_QCH - 1) / (2 * TW_QCH);
-	static const int wg_env = getenv("CHAINDP_TWIN_WG_PER_CU") ? atoi(getenv("CHAINDP_TWIN_WG_PER_CU")) : 0;   // (tuning: read once)
-	const int64_t cap = (int64_t)cus * (wg_env >= 1 && wg_env <= max_wg ? wg_env : max_wg);
+	const int64_t cap = (int64_t)cus * (wg_per_cu >= 1 && wg_per_cu <= max_wg ? wg_per_cu : max_wg);
 	if (blocks > cap) blocks = cap;
 	if (blocks < 1) blocks = 1;
-	blocks = (blocks + 7) & ~(int64_t)7;                           // eight grab counters, workgroup b on counter b mod 8: the same number of halves on each
+	return (blocks + 7) & ~(int64_t)7;                             // eight grab counters, workgroup b on counter b mod 8: the same number of halves on each
+}
+
+// DpDevice::twin_stamp: 12 words per workgroup of the largest grid on a device of `cus` CUs
+size_t twin_stamp_bytes(int cus) { return (size_t)twin_blocks(INT64_MAX / 2, cus, 32, 0) * 96; }
+
+// one launch of the layout ONE_LUT (the kernel returns at once when the batch is not for it)
+template <bool ONE_LUT>
+static hipError_t launch_twin_layout(const DpDevice &dev, hipStream_t st, TwinArgs g, int64_t max_units)
+{
+	const bool samegap = g.par.max_dist_y >= g.par.max_dist_x;
+	const int64_t blocks = twin_blocks(max_units, dev.cus, twin_max_wg_per_cu(samegap, ONE_LUT), dev.twin_wg_per_cu);
 	{
-		const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)d_queue, (int)(2 * blocks / 8), 8 * 64, st);   // every counter starts behind its halves' first grabs
+		const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)g.queue, (int)(2 * blocks / 8), 8 * 64, st);   // every counter starts behind its halves' first grabs
 		if (e != hipSuccess) return e;
 	}
 	// diagnostic: CHAINDP_TWIN_STAMP=1 makes the kernel stamp where its waves' time goes (s_memtime: shader-clock ticks) and this
 	// function print the averages -- it synchronises, so never set it in a timed run
-	static unsigned long long *d_stamp = nullptr;
-	const bool stamp = getenv("CHAINDP_TWIN_STAMP") != nullptr;
-	if (stamp && !d_stamp && hipMalloc((void**)&d_stamp, (size_t)cap * 96) != hipSuccess) d_stamp = nullptr;
-	g.stamp = stamp ? d_stamp : nullptr;
-	if (g.stamp) (void)hipMemsetAsync(d_stamp, 0, (size_t)blocks * 96, st);
-	{
-		hipFuncAttributes fa;                                        // LDS is addressed by raw byte offsets from 0: no static LDS may sit in front
-		const void *fn = samegap ? (const void*)k_chain_twin<true, ONE_LUT> : (const void*)k_chain_twin<false, ONE_LUT>;
-		const hipError_t e = hipFuncGetAttributes(&fa, fn);
-		if (e != hipSuccess) return e;
-		if (fa.sharedSizeBytes != 0) return hipErrorInvalidConfiguration;
-	}
+	g.stamp = dev.twin_stamp;
+	if (g.stamp) (void)hipMemsetAsync(g.stamp, 0, (size_t)blocks * 96, st);
 	if (samegap) hipLaunchKernelGGL((k_chain_twin<true, ONE_LUT>), dim3((unsigned)blocks), dim3(64), TwLayout<ONE_LUT>::BYTES, st, g);
 	else hipLaunchKernelGGL((k_chain_twin<false, ONE_LUT>), dim3((unsigned)blocks), dim3(64), TwLayout<ONE_LUT>::BYTES, st, g);
 	if (g.stamp) {
 		std::vector<unsigned long long> hb((size_t)blocks * 12);
-		if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(hb.data(), d_stamp, hb.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
+		if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(hb.data(), g.stamp, hb.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
 			double tot = 0, svc = 0, flush = 0, unit = 0, nsvc = 0, nfast = 0, nunit = 0, nb = 0, head = 0, take = 0, tail = 0, rounds = 0, nflush = 0;
 			for (int64_t b = 0; b < blocks; ++b) if (hb[(size_t)b * 12 + 7]) {
 				const unsigned long long *o = &hb[(size_t)b * 12];
@@ -1046,25 +1044,32 @@ static hipError_t launch_twin_layout(hipStream_t st, TwinArgs g, int64_t max_uni
 	return hipGetLastError();
 }
 
-hipError_t launch_chain_twin(hipStream_t st, const Params &par, int64_t max_units, const int64_t *d_off, const void *d_a,
-                             const unsigned long long *d_sumq, const uint16_t *d_lut, int lut_stride, const Unit *d_units,
-                             const unsigned long long *d_counters, int32_t *d_f, int32_t *d_p, int32_t *d_v,
-                             int32_t *d_first_child, uint8_t *d_flags, Unit *d_left, unsigned int *d_left_cnt, int force_left, int64_t total,
-                             const UnitAux *d_unit_aux, const unsigned int *d_key_range, unsigned int *d_route, unsigned int *d_queue, int two_tables)
+hipError_t launch_chain_twin(const DpDevice &dev, const DpBatch &b)
 {
+	const int64_t max_units = b.total / 2;
 	if (max_units <= 0) return hipSuccess;
-	if (!d_unit_aux || !d_key_range || !d_route || !d_queue) return hipErrorInvalidValue;
-	int dev = 0, cus = 256;
-	if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+	if (!b.aux || !b.key_range || !b.twin_queue) return hipErrorInvalidValue;
 	TwinArgs g;
-	g.par = par; g.off = d_off; g.a = (const ulonglong2*)d_a; g.sumq = d_sumq; g.lut = d_lut; g.lut_stride = lut_stride;
-	g.units = d_units; g.aux = d_unit_aux; g.counters = d_counters; g.f = d_f; g.p = d_p; g.v = d_v; g.first_child = d_first_child; g.flags = d_flags;
-	g.left = d_left; g.left_cnt = d_left_cnt; g.queue = d_queue; g.key_range = d_key_range; g.route = d_route; g.two_tables = two_tables != 0;
-	g.force_left = force_left; g.total = total; g.stamp = nullptr;
+	g.par = b.par; g.off = b.off; g.a = (const ulonglong2*)b.a; g.sumq = b.sumq; g.lut = b.lut; g.lut_stride = b.lut_stride;
+	if (b.n_segs) g.par.n_segs = 1;      // with per-read segment counts the units' UnitAux flags say which reads are multi-segment
+	                                     // (the batch-wide count is not used then, as in k_chain_units)
+	g.units = b.units; g.aux = b.aux; g.counters = b.counters; g.f = b.f; g.p = b.p; g.v = b.v; g.first_child = b.first_child; g.flags = b.flags;
+	g.left = b.left; g.left_cnt = b.hw.left_count(); g.queue = b.twin_queue; g.key_range = b.key_range; g.route = b.hw.route(); g.two_tables = b.two_tables != 0;
+	g.force_left = b.force_left; g.total = b.total; g.stamp = nullptr;
 	// both layouts, one table first: the device decides which one takes the batch (g.route), the other returns at once
-	hipError_t e = launch_twin_layout<true>(st, g, max_units, cus, d_queue);
-	if (e == hipSuccess) e = launch_twin_layout<false>(st, g, max_units, cus, d_queue);
+	hipError_t e = launch_twin_layout<true>(dev, b.st, g, max_units);
+	if (e == hipSuccess) e = launch_twin_layout<false>(dev, b.st, g, max_units);
 	return e;
+}
+
+// the instantiations of k_chain_twin (their LDS size is the layout's, fixed)
+int twin_kernels(DpKernel *out)
+{
+	out[0] = {(const void*)k_chain_twin<true, true>, "k_chain_twin<samegap, one table>", TwLayout<true>::BYTES};
+	out[1] = {(const void*)k_chain_twin<false, true>, "k_chain_twin<one table>", TwLayout<true>::BYTES};
+	out[2] = {(const void*)k_chain_twin<true, false>, "k_chain_twin<samegap, two tables>", TwLayout<false>::BYTES};
+	out[3] = {(const void*)k_chain_twin<false, false>, "k_chain_twin<two tables>", TwLayout<false>::BYTES};
+	return 4;
 }
 
 } // namespace chaindp

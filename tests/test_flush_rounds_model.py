@@ -1,6 +1,6 @@
 """CPU tier: the tile flush's v[] loop with its early exit (tests/flush_model.py) against the oracle's v, tile by tile, on the five
 seeded batches whose round counts motivated the exit and on hand-built units that need the late rounds.  The kernels' loops
-(chaindp_twin.hip, chaindp_quad.hip, fast_flush_tile in chaindp_fast.h) are this loop; test_gpu_flush_early_exit.py runs the same
+(chaindp_twin.hip, fast_flush_tile in chaindp_fast.h) are this loop; test_gpu_flush_early_exit.py runs the same
 inputs through them.
 
 What the data say (units of two anchors and more: a single anchor is settled without a flush), tiles by rounds started 0 .. 5:

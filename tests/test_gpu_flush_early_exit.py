@@ -1,7 +1,7 @@
 """GPU tier: every kernel that flushes tiles (the v[] loop with its early exit) on the inputs of test_flush_rounds_model.py -- the five
 seeded batches and the hand-built units that need rounds 4 to 6 and the count -- plus the small dense batch: k_chain_twin with one
 cost table per wave and with one per half, its hand-over modes (1: every unit to k_chain_units untouched, 2: after its first tile),
-k_chain_quad, and k_chain_dense / dense1 / dense16 behind k_chain_units (all three flush through fast_flush_tile).  f, p and v are
+and k_chain_dense / dense1 / dense16 behind k_chain_units (all three flush through fast_flush_tile).  f, p and v are
 compared element for element with the oracle, new_seed[] byte for byte with the oracle's compaction."""
 import numpy as np
 import pytest
@@ -68,20 +68,6 @@ def test_twin_layouts_and_handovers(dev, inputs, two, handover):
                 assert dev.twin_tables() == (2 if two else 1), (batch[0], dev.twin_tables())
     finally:
         dev.set_twin_tables(False)
-        dev.set_twin_handover(0)
-
-
-@pytest.mark.parametrize("handover", [0, 2])
-def test_quad(dev, inputs, handover):
-    dev.set_quad(True)
-    dev.set_twin_handover(handover)
-    try:
-        for i in (0, 1, 2, 5):
-            _check(dev, inputs[i], ("quad", handover))
-            if i != 5:
-                assert dev.quad_took(), inputs[i][0]
-    finally:
-        dev.set_quad(False)
         dev.set_twin_handover(0)
 
 
