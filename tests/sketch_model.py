@@ -70,8 +70,11 @@ def _rightmost_min(v, s, lo_d, hi_d):
     return bx, bt
 
 
-def sketch(seq, w, k, is_hpc, tile=256, traps=None):
+def sketch(seq, w, k, is_hpc, tile=256, traps=None, probe=None):
+    """probe: a dict that receives the intermediate quantities (what the edge tier's claims are proved from); it changes nothing."""
     assert 0 < w < 256 and 0 < k <= 28
+    if probe is not None:
+        probe.update(n_push=0, n_slots=0)
     c = NT4[np.frombuffer(bytes(seq), np.uint8)] if not isinstance(seq, np.ndarray) else NT4[seq]
     n = len(c)
     ex = np.zeros(0, np.uint64)
@@ -85,6 +88,8 @@ def sketch(seq, w, k, is_hpc, tile=256, traps=None):
         end = start = valid
     rank = tiled_rank(end, tile)
     P = int(end.sum())
+    if probe is not None:
+        probe.update(code=c, end=end, start=start, rank=rank, n_push=P)
     if P == 0:
         return ex, ex
     pe = np.zeros(P, np.int64); ps = np.zeros(P, np.int64); pc = np.zeros(P, np.uint64)
@@ -108,6 +113,8 @@ def sketch(seq, w, k, is_hpc, tile=256, traps=None):
     slot_flag[pe[~sym]] = True
     srank = tiled_rank(slot_flag, tile)
     S = int(slot_flag.sum())
+    if probe is not None:
+        probe.update(pend=pe, pstart=ps, sym=sym, slot_flag=slot_flag, n_slots=S)
     if S == 0:
         return ex, ex
     spos = np.nonzero(slot_flag)[0]
@@ -176,6 +183,8 @@ def sketch(seq, w, k, is_hpc, tile=256, traps=None):
         count("symmetric_skipped", sym.sum())
     es, eph, et = np.concatenate(em_s), np.concatenate(em_ph), np.concatenate(em_t)
     o = np.lexsort((et, eph, es))
+    if probe is not None:
+        probe.update(spos=spos, is_n=is_n, l=l, span=span, has=has, v=v, lcode=lcode, em_slot=es[o], em_phase=eph[o], em_target=et[o])
     return v[et[o]], y[et[o]]
 
 

@@ -5,8 +5,11 @@ Two tiers, and they are not worth the same:
     unmodified reference's collect_minimizers) and the `mini` arrays of the older seed fixtures, sketched here from tests/golden/fa/.
   * restatement tier -- even k, w up to 255, w >= k + 2, the bytes 0..3 and multi-segment reads cannot be produced by the reference's
     dumper (its presets do not reach them).  There the model is held to `loop_sketch` below, a per-base loop with a ring of w
-    entries written for this test from the loop's semantics.  That is restatement against restatement: it shows that the parallel
-    formulation equals the sequential one, not that either equals the reference.
+    entries written for this test from the loop's semantics: restatement against restatement, which shows that the parallel
+    formulation equals the sequential one.  The reference's mm_sketch itself takes w, k and is_hpc as arguments, so where
+    oracle/_ref/libmm2sketch_ref.so is built (tests/sketch_ref.py) the same inputs are also held to the unmodified reference,
+    minimizer for minimizer.  Where it is not built, this tier is tied to the reference through the recorded results of the edge
+    cases (tests/test_sketch_edge_shapes_cpu.py), which sit in the same region.
 The model's tiled scans are also run with every tile size: the cut between tiles must never show."""
 import glob
 import os
@@ -16,6 +19,7 @@ import numpy as np
 import pytest
 
 import sketch_model as sm
+import sketch_ref as sr
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SKETCH = sorted(glob.glob(os.path.join(HERE, "golden", "sketch", "*.npz")))
@@ -166,6 +170,8 @@ def test_restatement_tier_model_equals_per_base_loop():
         x, y = sm.sketch(s, w, k, hpc, tile=rnd.choice([64, 256, 1024]), traps=traps)
         lx, ly = loop_sketch(s, w, k, hpc)
         assert np.array_equal(x, lx) and np.array_equal(y, ly), (it, len(s), w, k, hpc)
+        if sr.have():
+            assert np.stack((x, y), 1).tobytes() == sr.sketch(s, w, k, hpc).tobytes(), (it, len(s), w, k, hpc)
     for name in ("symmetric_skipped", "final_stale_beats_fresh", "span_ge_256_slot", "first_window_tie", "rescan_tie"):
         assert traps.get(name, 0) > 0, (name, traps)
 
@@ -183,3 +189,6 @@ def test_restatement_tier_multi_segment_reads():
             x, y = loop_sketch(seqs[q], 5, 15, 0)
             want.append(np.stack((x, y + np.uint64((rid << 32) + (shift << 1))), 1)); shift += len(seqs[q]); q += 1
     assert np.array_equal(mini, np.concatenate(want)) and off[-1] == len(mini) and len(off) == len(segs) + 1
+    if sr.have():
+        r_off, r_mini = sr.sketch_batch(seq, seq_off, 5, 15, 0, n_segs_per_read=segs)
+        assert np.array_equal(off, r_off) and mini.tobytes() == r_mini.tobytes()
