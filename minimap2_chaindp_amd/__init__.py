@@ -4,6 +4,7 @@ The product is the C-ABI library csrc/libchaindp_hip.so (include/chaindp.h, incl
 this package is its host-side mirror for tests and benchmarks:
   chaindp    ctypes front end of the batch API (HIP kernels; no CPU fallback)
   fpga       the reference's packet-level driver ABI (fpga.h) as served by the library
+  _cabi      the ctypes prototypes of both, read from the headers under include/
   params     DP parameter presets as the reference derives them
   anchorgen  seeded ONT-shaped synthetic anchor batches
   shard      read sharding across the GPUs of a node

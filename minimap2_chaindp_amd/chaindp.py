@@ -10,7 +10,8 @@ import os
 
 import numpy as np
 
-from .params import ChainParams, PostOpt
+
+from . import _cabi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CHAINDP_LIB: an alternative build of the same library (A/B timing of kernel variants on one box, tools/ab.sh)
@@ -19,21 +20,7 @@ LIB_PATH = os.environ.get("CHAINDP_LIB") or os.path.join(_HERE, "csrc", "libchai
 SEED_DTYPE = np.dtype([("x", "<u8"), ("y", "<u8"), ("p", "<i4"), ("f", "<i4")])  # struct new_seed (minimap.h:51-55)
 
 # every symbol include/chaindp.h declares (tests check the library exports all of them)
-ABI_SYMBOLS = (
-    "chaindp_device_count", "chaindp_create", "chaindp_destroy", "chaindp_last_error", "chaindp_chain_batch",
-    "chaindp_upload", "chaindp_run", "chaindp_sync", "chaindp_download", "chaindp_compact",
-    "chaindp_upload_gather", "chaindp_compact_offsets", "chaindp_download_seeds", "chaindp_host_alloc",
-    "chaindp_host_free", "chaindp_run_device", "chaindp_set_profiling", "chaindp_get_kernel_ms",
-    "chaindp_get_stats", "chaindp_set_ring", "chaindp_run_full", "chaindp_set_variant", "chaindp_upload_gather_ex", "chaindp_scatter_seeds", "chaindp_backtrack",
-    "chaindp_index_create", "chaindp_index_destroy", "chaindp_collect_seeds", "chaindp_download_mini_pos", "chaindp_download_anchors", "chaindp_collect_seeds_gather", "chaindp_scatter_mini_pos",
-    "chaindp_gen_regs", "chaindp_est_err",
-    "chaindp_pipe_create", "chaindp_pipe_destroy", "chaindp_pipe_submit", "chaindp_pipe_wait", "chaindp_pipe_release",
-    "chaindp_pipe_last_error", "chaindp_map_batch",
-    "chaindp_chain_post", "chaindp_map_reads", "chaindp_post_logf_selftest", "chaindp_post_logf_patches",
-    "chaindp_sketch", "chaindp_download_minimizers", "chaindp_map_seqs", "chaindp_get_sketch_ms",
-    "chaindp_frag_post", "chaindp_map_frags", "chaindp_map_frag_seqs",
-    "chaindp_index_build", "chaindp_index_build_status", "chaindp_index_sizes", "chaindp_index_download", "chaindp_index_cal_max_occ",
-)
+ABI_SYMBOLS = tuple(_cabi.prototypes("chaindp.h"))
 
 # chaindp_reg_t == mm_reg1_t (minimap.h:100-115), 80 bytes; `bits` is the bit-field word (rev = bit 10)
 REG_DTYPE = np.dtype([(k, "<i4") for k in ("id", "cnt", "rid", "score", "qs", "qe", "rs", "re", "parent", "subsc", "as", "mlen", "blen", "n_sub", "score0")]
@@ -48,91 +35,13 @@ _lib = None
 
 
 def lib():
+    """The library, every function of include/chaindp.h and include/chaindp_debug.h bound with the header's prototype."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise ChainDPError(f"{LIB_PATH} is missing: build it with __graft_entry__.build() "
                                "(make -C minimap2_chaindp_amd/csrc); there is no fallback path")
-        L = C.CDLL(LIB_PATH)
-        P = C.POINTER(ChainParams)
-        vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int
-        L.chaindp_device_count.restype = i32
-        L.chaindp_create.restype = vp
-        L.chaindp_create.argtypes = [i32, i64, i64]
-        L.chaindp_destroy.argtypes = [vp]
-        L.chaindp_last_error.restype = C.c_char_p
-        L.chaindp_last_error.argtypes = [vp]
-        L.chaindp_chain_batch.argtypes = [vp, P, i64, vp, vp, vp, vp, vp, vp]
-        L.chaindp_upload.argtypes = [vp, i64, vp, vp, vp]
-        L.chaindp_run.argtypes = [vp, P]
-        L.chaindp_run_full.argtypes = [vp, P]
-        L.chaindp_sync.argtypes = [vp]
-        L.chaindp_download.argtypes = [vp, vp, vp, vp]
-        L.chaindp_compact.argtypes = [vp, P, vp, vp]
-        L.chaindp_upload_gather.argtypes = [vp, i64, vp, vp, vp]
-        L.chaindp_compact_offsets.argtypes = [vp, P, vp]
-        L.chaindp_download_seeds.argtypes = [vp, i64, i64, vp]
-        L.chaindp_host_alloc.restype = vp
-        L.chaindp_host_alloc.argtypes = [C.c_size_t]
-        L.chaindp_host_free.argtypes = [vp]
-        L.chaindp_run_device.argtypes = [vp, P, i64, i64, vp, vp, vp, vp, vp, vp, vp]
-        L.chaindp_set_profiling.argtypes = [vp, i32]
-        L.chaindp_get_kernel_ms.argtypes = [vp, vp, vp, i32]
-        L.chaindp_get_stats.argtypes = [vp, vp]
-        L.chaindp_set_ring.argtypes = [vp, i32]
-        L.chaindp_set_variant.argtypes = [vp, i32]
-        L.chaindp_backtrack.argtypes = [vp, P, i32, vp, vp, vp, vp]
-        L.chaindp_gen_regs.argtypes = [vp, vp, vp, vp]
-        L.chaindp_est_err.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
-        L.chaindp_index_create.restype = vp
-        L.chaindp_index_create.argtypes = [i32, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
-        L.chaindp_index_destroy.restype = None
-        L.chaindp_index_destroy.argtypes = [vp]
-        L.chaindp_index_build.restype = vp
-        L.chaindp_index_build.argtypes = [vp, i32, i32, i32, i32, i64, vp, vp, vp]
-        L.chaindp_index_build_status.argtypes = [vp]
-        L.chaindp_index_sizes.argtypes = [vp, vp]
-        L.chaindp_index_download.argtypes = [vp, vp, vp, vp, vp]
-        L.chaindp_index_cal_max_occ.argtypes = [vp, C.c_float, vp]
-        L.chaindp_debug_index_from_minimizers.restype = vp
-        L.chaindp_debug_index_from_minimizers.argtypes = [vp, i32, i64, vp, i64, vp]
-        L.chaindp_debug_index_chunk_bases.argtypes = [vp, i64]
-        L.chaindp_debug_index_route.argtypes = [vp, vp]
-        L.chaindp_debug_index_stage_ms.argtypes = [vp, vp]
-        L.chaindp_collect_seeds.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.chaindp_download_mini_pos.argtypes = [vp, vp]
-        L.chaindp_collect_seeds_gather.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.chaindp_scatter_mini_pos.argtypes = [vp, i64, vp]
-        L.chaindp_upload_gather_ex.argtypes = [vp, i64, vp, vp, vp, i32]
-        L.chaindp_scatter_seeds.argtypes = [vp, i64, vp]
-        L.chaindp_device_count.argtypes = []
-        L.chaindp_download_anchors.argtypes = [vp, vp]
-        L.chaindp_map_batch.argtypes = [vp, vp, i32, i32, P, i32, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp]
-        PO = C.POINTER(PostOpt)
-        L.chaindp_chain_post.argtypes = [vp, PO, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp]
-        L.chaindp_map_reads.argtypes = [vp, vp, i32, i32, P, i32, PO, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, i64, vp, vp]
-        L.chaindp_sketch.argtypes = [vp, i32, i32, i32, i64, vp, vp, vp, vp]
-        L.chaindp_download_minimizers.argtypes = [vp, vp]
-        L.chaindp_map_seqs.argtypes = [vp, vp, i32, i32, i32, i32, i32, P, i32, PO, i64, vp, vp, vp, vp, vp, i32, vp, vp, i64, vp, vp]
-        L.chaindp_get_sketch_ms.argtypes = [vp, vp, vp, i32]
-        L.chaindp_frag_post.argtypes = [vp, PO, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp]
-        L.chaindp_map_frags.argtypes = [vp, vp, i32, i32, P, i32, PO, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, i32, vp, vp, i64, vp, vp]
-        L.chaindp_map_frag_seqs.argtypes = [vp, vp, i32, i32, i32, i32, i32, P, i32, PO, i32, i64, i64, vp, vp, vp, vp, vp, vp, i32, vp, vp, i64, vp, vp]
-        L.chaindp_debug_set_frag_lds_cap.argtypes = [vp, i32]
-        L.chaindp_post_logf_selftest.restype = i64
-        L.chaindp_post_logf_selftest.argtypes = [vp, i32]
-        L.chaindp_post_logf_patches.restype = i64
-        L.chaindp_post_logf_patches.argtypes = [vp, vp, i64]
-        L.chaindp_pipe_create.restype = vp
-        L.chaindp_pipe_create.argtypes = [i32, i32, i64, i64]
-        L.chaindp_pipe_destroy.restype = None
-        L.chaindp_pipe_destroy.argtypes = [vp]
-        L.chaindp_pipe_submit.argtypes = [vp, P, i64, vp, vp, vp, i64]
-        L.chaindp_pipe_wait.argtypes = [vp, vp]
-        L.chaindp_pipe_release.argtypes = [vp]
-        L.chaindp_pipe_last_error.restype = C.c_char_p
-        L.chaindp_pipe_last_error.argtypes = [vp]
-        _lib = L
+        _lib = _cabi.bind(C.CDLL(LIB_PATH), "chaindp.h", "chaindp_debug.h")
     return _lib
 
 
@@ -152,6 +61,34 @@ def device_count():
 
 def _ptr(a):
     return None if a is None else a.ctypes.data
+
+
+def _ptr0(a):
+    """_ptr, but an empty array goes as NULL too."""
+    return None if a is None or not len(a) else a.ctypes.data
+
+
+def _arr(x, dtype):
+    """x as a C-contiguous array of dtype; None stays None (the C side's "not given")."""
+    return None if x is None else np.ascontiguousarray(x, dtype)
+
+
+# What the calls that return hits do about the room for them.  regs_cap=None allocates max(source // divisor, REGS_CAP_FLOOR) records
+# (floored=False: at least 1), where source is the batch's minimizer count ("n_mini"), its bases ("n_bases") or the resident batch's
+# anchors ("total").  When the C call answers CHAINDP_ERR_CAPACITY with more hits than that: a guess is always retried, a cap the
+# caller gave is retried or raises (explicit); retry names the call that fetches the hits with the exact count ("again": the whole
+# call once more, None: nothing to retry with).  state: _n_reads / _total follow the batch "before" or "after" rc is looked at.
+REGS_CAP_FLOOR = 1024
+_Cap = collections.namedtuple("_Cap", "source divisor floored explicit retry state")
+_CAPS = {
+    "map_batch":     _Cap("n_mini",  4,  True,  "retry", "gen_regs",   "after"),
+    "chain_post":    _Cap("total",   1,  False, "raise", None,         None),      # room for every input hit: never short
+    "map_reads":     _Cap("n_mini",  4,  True,  "retry", "chain_post", "before"),
+    "map_seqs":      _Cap("n_bases", 32, True,  "retry", "chain_post", "before"),
+    "frag_post":     _Cap("total",   4,  True,  "raise", "again",      None),
+    "map_frags":     _Cap("n_mini",  2,  True,  "raise", "frag_post",  "before"),
+    "map_frag_seqs": _Cap("n_bases", 16, True,  "raise", "again",      "before"),  # again: the flip is part of the call
+}
 
 
 class Device:
@@ -270,15 +207,12 @@ class Device:
     def est_err(self, regs_off, regs, qlen, ref_len, mini_pos_off=None, mini_pos=None):
         """mm_est_err on the hits `regs` (REG_DTYPE, read r owns regs_off[r]:regs_off[r+1]) -> (regs with div, n_match, n_tot).
         mini_pos_off / mini_pos None: the minimizer positions collect_seeds() left on the device."""
-        regs_off = np.ascontiguousarray(regs_off, np.int64)
-        regs = np.ascontiguousarray(regs, REG_DTYPE).copy()
-        qlen = np.ascontiguousarray(qlen, np.int32)
-        ref_len = np.ascontiguousarray(ref_len, np.int32)
+        regs_off, regs = _arr(regs_off, np.int64), _arr(regs, REG_DTYPE).copy()
+        qlen, ref_len = _arr(qlen, np.int32), _arr(ref_len, np.int32)
         mt = np.zeros((max(len(regs), 1), 2), np.int32)
-        mpo = None if mini_pos_off is None else np.ascontiguousarray(mini_pos_off, np.int64)
-        mp = None if mini_pos is None else np.ascontiguousarray(mini_pos, np.uint64)
-        self._check(self._lib.chaindp_est_err(self._ctx, _ptr(regs_off), _ptr(regs) if len(regs) else None, _ptr(qlen), _ptr(ref_len) if len(ref_len) else None,
-                                              len(ref_len), None if mpo is None else _ptr(mpo), None if mp is None or not len(mp) else _ptr(mp), _ptr(mt)))
+        mpo, mp = _arr(mini_pos_off, np.int64), _arr(mini_pos, np.uint64)
+        self._check(self._lib.chaindp_est_err(self._ctx, _ptr(regs_off), _ptr0(regs), _ptr(qlen), _ptr0(ref_len), len(ref_len), _ptr(mpo), _ptr0(mp),
+                                              _ptr(mt)))
         return regs, mt[:len(regs), 0].copy(), mt[:len(regs), 1].copy()
 
     # -- seed collection on the GPU (collect_seed_hits, map.c:187-236, over the FPGA index image)
@@ -350,19 +284,21 @@ class Device:
         self._check(self._lib.chaindp_debug_index_stage_ms(index, _ptr(ms)))
         return ms.tolist()
 
+    def _minimizers(self, mini_off, mini, bid):
+        """(mini_off, mini, n_reads, n_mini) of the caller's minimizers; mini_off = mini = None: of the ones the last sketch() left on
+        the device, which go to the C side as two NULLs."""
+        if mini_off is None and mini is None:
+            return None, None, len(bid), self._sk_n_mini
+        mini_off, mini = np.ascontiguousarray(mini_off, np.int64), np.ascontiguousarray(mini, np.uint64).reshape(-1, 2)
+        return mini_off, mini, len(mini_off) - 1, len(mini)
+
     def collect_seeds(self, index, flag, max_occ, mini_off, mini, bid, qlen, n_segs=None):
         """Minimizers of a batch -> sorted anchors resident on the device (as after upload()).  Returns (off int64[n_reads+1],
         anchors uint64[n,2], rep_len int32[n_reads], mini_pos_off, mini_pos uint64[...]).  mini_off = mini = None: the minimizers the last
         sketch() left on the device (qlen = None then: the lengths it saw)."""
-        if mini_off is None and mini is None:
-            n_reads = len(bid)
-        else:
-            mini_off = np.ascontiguousarray(mini_off, np.int64)
-            n_reads = len(mini_off) - 1
-            mini = np.ascontiguousarray(mini, np.uint64).reshape(-1, 2)
-        bid = np.ascontiguousarray(bid, np.uint32); qlen = None if qlen is None else np.ascontiguousarray(qlen, np.int32)
+        mini_off, mini, n_reads, _ = self._minimizers(mini_off, mini, bid)
+        bid, qlen, ns = _arr(bid, np.uint32), _arr(qlen, np.int32), _arr(n_segs, np.int32)
         off = np.zeros(n_reads + 1, np.int64); mpo = np.zeros(n_reads + 1, np.int64); rep = np.zeros(max(n_reads, 1), np.int32)
-        ns = None if n_segs is None else np.ascontiguousarray(n_segs, np.int32)
         self._check(self._lib.chaindp_collect_seeds(self._ctx, index, int(flag), int(max_occ), n_reads, _ptr(mini_off), _ptr(mini), _ptr(bid),
                                                     _ptr(qlen), _ptr(ns), _ptr(off), _ptr(rep), _ptr(mpo)))
         self._n_reads, self._total = n_reads, int(off[-1])
@@ -372,75 +308,76 @@ class Device:
         self._check(self._lib.chaindp_download_mini_pos(self._ctx, _ptr(mp)))
         return off, a[:self._total], rep[:n_reads], mpo, mp[:int(mpo[-1])]
 
+    # -- the calls that return hits: one path, what differs between them is the C call and their row of _CAPS
+    def _hits(self, method, regs_cap, n_off, call, n_reads=None, again=(), **size):
+        """Allocates the outputs, makes the C call -- call(off, regs, cap, rep_len, n_anchors) -> rc -- and deals with a buffer that was
+        too small as the method's row of _CAPS says: (off int64[n_off + 1], regs REG_DTYPE[off[-1]], rep_len int32[n_reads], n_anchors).
+        n_reads None: a post step on the resident batch (no rep_len, no n_anchors, _n_reads / _total stay).  again: the leading
+        arguments of the row's retry call; size: the row's source where it is not _total."""
+        row = _CAPS[method]
+        source = self._total if row.source == "total" else size[row.source]
+        cap = int(regs_cap) if regs_cap is not None else max(source // row.divisor, REGS_CAP_FLOOR if row.floored else 1)
+        while True:
+            off, regs, na = np.zeros(n_off + 1, np.int64), np.zeros(max(cap, 1), REG_DTYPE), C.c_int64(0)
+            rep = None if n_reads is None else np.zeros(max(n_reads, 1), np.int32)
+            rc = call(off, regs, cap, rep, na)
+            if row.state == "before":
+                self._n_reads, self._total = n_reads, int(na.value)
+            n = int(off[-1])
+            short = rc == -2 and n > cap and row.retry is not None and (regs_cap is None or row.explicit == "retry")
+            if not (short and row.retry == "again"):
+                break
+            cap = n                                                            # more hits than guessed: again with room for them
+        if not short:
+            self._check(rc)
+        elif row.retry == "gen_regs":                                          # the hits are resident: fetch them
+            regs = self.gen_regs(*again, n)
+        else:                                                                  # run the post steps again with room for them
+            off, regs = getattr(self, row.retry)(*again, regs_cap=n)
+        if row.state == "after":
+            self._n_reads, self._total = n_reads, int(na.value)
+        return off, regs[:int(off[-1])], None if rep is None else rep[:n_reads], int(na.value)
+
     def map_batch(self, index, flag, max_occ, par, min_cnt, mini_off, mini, bid, qlen, hash_, regs_cap=None):
         """Minimizers in, hits out, everything in between resident (chaindp_map_batch): (regs_off int64[n_reads+1], regs REG_DTYPE[...],
         rep_len int32[n_reads], n_anchors)."""
-        mini_off = np.ascontiguousarray(mini_off, np.int64)
+        mini_off, mini = _arr(mini_off, np.int64), _arr(mini, np.uint64).reshape(-1, 2)
         n_reads = len(mini_off) - 1
-        mini = np.ascontiguousarray(mini, np.uint64).reshape(-1, 2)
-        bid = np.ascontiguousarray(bid, np.uint32); qlen = np.ascontiguousarray(qlen, np.int32); hash_ = np.ascontiguousarray(hash_, np.uint32)
-        cap = int(regs_cap) if regs_cap is not None else max(len(mini) // 4, 1024)
-        roff = np.zeros(n_reads + 1, np.int64); rep = np.zeros(max(n_reads, 1), np.int32)
-        regs = np.zeros(max(cap, 1), REG_DTYPE)
-        na = C.c_int64(0)
-        rc = self._lib.chaindp_map_batch(self._ctx, index, int(flag), int(max_occ), C.byref(par), int(min_cnt), n_reads, _ptr(mini_off), _ptr(mini),
-                                         _ptr(bid), _ptr(qlen), _ptr(hash_), _ptr(roff), _ptr(regs), cap, _ptr(rep), C.byref(na))
-        if rc == -2 and int(roff[-1]) > cap:                                   # more hits than guessed: they are resident, fetch them
-            regs = self.gen_regs(hash_, qlen, int(roff[-1]))
-        else:
-            self._check(rc)
-        self._n_reads, self._total = n_reads, int(na.value)
-        return roff, regs[:int(roff[-1])], rep[:n_reads], int(na.value)
+        bid, qlen, hash_ = _arr(bid, np.uint32), _arr(qlen, np.int32), _arr(hash_, np.uint32)
+
+        def call(roff, regs, cap, rep, na):
+            return self._lib.chaindp_map_batch(self._ctx, index, int(flag), int(max_occ), C.byref(par), int(min_cnt), n_reads, _ptr(mini_off), _ptr(mini),
+                                               _ptr(bid), _ptr(qlen), _ptr(hash_), _ptr(roff), _ptr(regs), cap, _ptr(rep), C.byref(na))
+        return self._hits("map_batch", regs_cap, n_reads, call, n_reads, again=(hash_, qlen), n_mini=len(mini))
 
     # -- chain_post + mm_est_err + mm_set_mapq (map.c:870-877, one segment, no alignment), after gen_regs() / map_batch()
     def chain_post(self, opt, ref_len, qlen=None, rep_len=None, mini_pos_off=None, mini_pos=None, regs_cap=None, want_anchors=False):
         """The final hits of every read (chaindp_chain_post) from the hits gen_regs() left on the device: (regs_off int64[n_reads+1],
         regs REG_DTYPE[...]) and, with want_anchors, (a_off int64[n_reads+1], a uint64[...,2]): the anchors as chain_post left them.
         qlen / rep_len / mini_pos None: the ones already on the device.  regs_cap None: room for every input hit (never fewer)."""
-        n_reads = self._n_reads
-        ref_len = np.ascontiguousarray(ref_len, np.int32)
-        ql = None if qlen is None else np.ascontiguousarray(qlen, np.int32)
-        rl = None if rep_len is None else np.ascontiguousarray(rep_len, np.int32)
-        mpo = None if mini_pos_off is None else np.ascontiguousarray(mini_pos_off, np.int64)
-        mp = None if mini_pos is None else np.ascontiguousarray(mini_pos, np.uint64)
-        cap = int(regs_cap) if regs_cap is not None else max(self._total, 1)
-        roff = np.zeros(n_reads + 1, np.int64)
-        regs = np.zeros(max(cap, 1), REG_DTYPE)
-        aoff = np.zeros(n_reads + 1, np.int64) if want_anchors else None
+        ref_len, ql, rl = _arr(ref_len, np.int32), _arr(qlen, np.int32), _arr(rep_len, np.int32)
+        mpo, mp = _arr(mini_pos_off, np.int64), _arr(mini_pos, np.uint64)
+        aoff = np.zeros(self._n_reads + 1, np.int64) if want_anchors else None
         a = np.zeros((max(self._total, 1), 2), np.uint64) if want_anchors else None
-        self._check(self._lib.chaindp_chain_post(self._ctx, C.byref(opt), _ptr(ql), _ptr(rl), _ptr(ref_len) if len(ref_len) else None, len(ref_len),
-                                                 _ptr(mpo), None if mp is None or not len(mp) else _ptr(mp), _ptr(roff), _ptr(regs), cap,
-                                                 _ptr(aoff), _ptr(a)))
-        regs = regs[:int(roff[-1])]
+
+        def call(roff, regs, cap, rep, na):
+            return self._lib.chaindp_chain_post(self._ctx, C.byref(opt), _ptr(ql), _ptr(rl), _ptr0(ref_len), len(ref_len), _ptr(mpo), _ptr0(mp),
+                                                _ptr(roff), _ptr(regs), cap, _ptr(aoff), _ptr(a))
+        roff, regs, _, _ = self._hits("chain_post", regs_cap, self._n_reads, call)
         return (roff, regs, aoff, a[:int(aoff[-1])]) if want_anchors else (roff, regs)
 
     def map_reads(self, index, flag, max_occ, par, min_cnt, opt, mini_off, mini, bid, qlen, hash_, ref_len, regs_cap=None):
         """Minimizers in, final hits out (chaindp_map_reads): (regs_off int64[n_reads+1], regs REG_DTYPE[...], rep_len int32[n_reads],
         n_anchors).  regs_cap None: a guess from the minimizer count, retried with the exact count if the hits need more.
         mini_off = mini = None: the minimizers the last sketch() left on the device (qlen = None then: the lengths it saw)."""
-        if mini_off is None and mini is None:
-            n_reads, n_mini = len(bid), self._sk_n_mini
-        else:
-            mini_off = np.ascontiguousarray(mini_off, np.int64)
-            n_reads = len(mini_off) - 1
-            mini = np.ascontiguousarray(mini, np.uint64).reshape(-1, 2)
-            n_mini = len(mini)
-        bid = np.ascontiguousarray(bid, np.uint32); hash_ = np.ascontiguousarray(hash_, np.uint32)
-        qlen = None if qlen is None else np.ascontiguousarray(qlen, np.int32)
-        ref_len = np.ascontiguousarray(ref_len, np.int32)
-        cap = int(regs_cap) if regs_cap is not None else max(n_mini // 4, 1024)
-        roff = np.zeros(n_reads + 1, np.int64); rep = np.zeros(max(n_reads, 1), np.int32)
-        regs = np.zeros(max(cap, 1), REG_DTYPE)
-        na = C.c_int64(0)
-        rc = self._lib.chaindp_map_reads(self._ctx, index, int(flag), int(max_occ), C.byref(par), int(min_cnt), C.byref(opt), n_reads, _ptr(mini_off),
-                                         _ptr(mini), _ptr(bid), _ptr(qlen), _ptr(hash_), _ptr(ref_len) if len(ref_len) else None, len(ref_len),
-                                         _ptr(roff), _ptr(regs), cap, _ptr(rep), C.byref(na))
-        self._n_reads, self._total = n_reads, int(na.value)
-        if rc == -2 and int(roff[-1]) > cap:                                   # more hits than guessed: run the post steps again with room for them
-            roff, regs = self.chain_post(opt, ref_len, regs_cap=int(roff[-1]))
-        else:
-            self._check(rc)
-        return roff, regs[:int(roff[-1])], rep[:n_reads], int(na.value)
+        mini_off, mini, n_reads, n_mini = self._minimizers(mini_off, mini, bid)
+        bid, qlen, hash_, ref_len = _arr(bid, np.uint32), _arr(qlen, np.int32), _arr(hash_, np.uint32), _arr(ref_len, np.int32)
+
+        def call(roff, regs, cap, rep, na):
+            return self._lib.chaindp_map_reads(self._ctx, index, int(flag), int(max_occ), C.byref(par), int(min_cnt), C.byref(opt), n_reads, _ptr(mini_off),
+                                               _ptr(mini), _ptr(bid), _ptr(qlen), _ptr(hash_), _ptr0(ref_len), len(ref_len), _ptr(roff), _ptr(regs), cap,
+                                               _ptr(rep), C.byref(na))
+        return self._hits("map_reads", regs_cap, n_reads, call, n_reads, again=(opt, ref_len), n_mini=n_mini)
 
     # -- sketch on the device: bases in, minimizers resident (chaindp_sketch)
     @staticmethod
@@ -471,20 +408,13 @@ class Device:
         """Bases in, final hits out (chaindp_map_seqs = sketch() + map_reads()): (regs_off, regs, rep_len, n_anchors)."""
         seq, seq_off = self._seqs(seq, seq_off)
         n_reads = len(seq_off) - 1
-        bid = np.ascontiguousarray(bid, np.uint32); hash_ = np.ascontiguousarray(hash_, np.uint32); ref_len = np.ascontiguousarray(ref_len, np.int32)
-        cap = int(regs_cap) if regs_cap is not None else max(len(seq) // 32, 1024)
-        roff = np.zeros(n_reads + 1, np.int64); rep = np.zeros(max(n_reads, 1), np.int32)
-        regs = np.zeros(max(cap, 1), REG_DTYPE)
-        na = C.c_int64(0)
-        rc = self._lib.chaindp_map_seqs(self._ctx, index, int(w), int(k), int(bool(is_hpc)), int(flag), int(max_occ), C.byref(par), int(min_cnt), C.byref(opt),
-                                        n_reads, _ptr(seq_off), _ptr(seq) if len(seq) else None, _ptr(bid), _ptr(hash_), _ptr(ref_len) if len(ref_len) else None,
-                                        len(ref_len), _ptr(roff), _ptr(regs), cap, _ptr(rep), C.byref(na))
-        self._n_reads, self._total = n_reads, int(na.value)
-        if rc == -2 and int(roff[-1]) > cap:                                   # more hits than guessed: run the post steps again with room for them
-            roff, regs = self.chain_post(opt, ref_len, regs_cap=int(roff[-1]))
-        else:
-            self._check(rc)
-        return roff, regs[:int(roff[-1])], rep[:n_reads], int(na.value)
+        bid, hash_, ref_len = _arr(bid, np.uint32), _arr(hash_, np.uint32), _arr(ref_len, np.int32)
+
+        def call(roff, regs, cap, rep, na):
+            return self._lib.chaindp_map_seqs(self._ctx, index, int(w), int(k), int(bool(is_hpc)), int(flag), int(max_occ), C.byref(par), int(min_cnt),
+                                              C.byref(opt), n_reads, _ptr(seq_off), _ptr0(seq), _ptr(bid), _ptr(hash_), _ptr0(ref_len), len(ref_len),
+                                              _ptr(roff), _ptr(regs), cap, _ptr(rep), C.byref(na))
+        return self._hits("map_seqs", regs_cap, n_reads, call, n_reads, again=(opt, ref_len), n_bases=len(seq))
 
     # -- reads of several segments (paired reads): chain_post with mm_select_sub_multi, mm_seg_gen, per-segment mm_set_parent / mm_set_mapq
     def frag_post(self, opt, ref_len, n_segs, seg_len=None, rep_len=None, mini_pos_off=None, mini_pos=None, regs_cap=None, want_anchors=False):
@@ -492,85 +422,49 @@ class Device:
         regs REG_DTYPE[...]) and, with want_anchors, (seg_a_off int64[n_seqs+1], seg_a uint64[...,2]): every segment's anchors.  n_segs
         int32[n_reads]: the segments of every read (1..255), as the batch was chained; seg_len int32[n_seqs] (None: the lengths the last
         sketch() saw); rep_len / mini_pos None: the ones on the device.  regs_cap None: retried with the exact count if a guess is short."""
-        ns = np.ascontiguousarray(n_segs, np.int32)
+        ns = _arr(n_segs, np.int32)
         n_seqs = int(ns.sum())
-        ref_len = np.ascontiguousarray(ref_len, np.int32)
-        sl = None if seg_len is None else np.ascontiguousarray(seg_len, np.int32)
-        rl = None if rep_len is None else np.ascontiguousarray(rep_len, np.int32)
-        mpo = None if mini_pos_off is None else np.ascontiguousarray(mini_pos_off, np.int64)
-        mp = None if mini_pos is None else np.ascontiguousarray(mini_pos, np.uint64)
-        cap = int(regs_cap) if regs_cap is not None else max(self._total // 4, 1024)
+        ref_len, sl, rl = _arr(ref_len, np.int32), _arr(seg_len, np.int32), _arr(rep_len, np.int32)
+        mpo, mp = _arr(mini_pos_off, np.int64), _arr(mini_pos, np.uint64)
         aoff = np.zeros(n_seqs + 1, np.int64) if want_anchors else None
         a = np.zeros((max(self._total, 1), 2), np.uint64) if want_anchors else None
-        while True:
-            soff = np.zeros(n_seqs + 1, np.int64)
-            regs = np.zeros(max(cap, 1), REG_DTYPE)
-            rc = self._lib.chaindp_frag_post(self._ctx, C.byref(opt), n_seqs, _ptr(ns), _ptr(sl), _ptr(rl), _ptr(ref_len) if len(ref_len) else None,
-                                             len(ref_len), _ptr(mpo), None if mp is None or not len(mp) else _ptr(mp), _ptr(soff), _ptr(regs), cap,
-                                             _ptr(aoff), _ptr(a))
-            if rc == -2 and regs_cap is None and int(soff[-1]) > cap:          # more hits than guessed: again with room for them
-                cap = int(soff[-1])
-                continue
-            self._check(rc)
-            break
-        regs = regs[:int(soff[-1])]
+
+        def call(soff, regs, cap, rep, na):
+            return self._lib.chaindp_frag_post(self._ctx, C.byref(opt), n_seqs, _ptr(ns), _ptr(sl), _ptr(rl), _ptr0(ref_len), len(ref_len), _ptr(mpo),
+                                               _ptr0(mp), _ptr(soff), _ptr(regs), cap, _ptr(aoff), _ptr(a))
+        soff, regs, _, _ = self._hits("frag_post", regs_cap, n_seqs, call)
         return (soff, regs, aoff, a[:int(aoff[-1])]) if want_anchors else (soff, regs)
 
     def map_frags(self, index, flag, max_occ, par, min_cnt, opt, mini_off, mini, bid, qlen, hash_, n_segs, seg_len, ref_len, regs_cap=None):
         """Minimizers in, per-segment final hits out (chaindp_map_frags): (seg_regs_off int64[n_seqs+1], regs REG_DTYPE[...], rep_len
         int32[n_reads], n_anchors).  mini_off = mini = None: the minimizers the last sketch() left on the device (qlen = seg_len = None
         then: the lengths it saw).  One `par` per call: group reads by their gap parameters."""
-        ns = np.ascontiguousarray(n_segs, np.int32)
+        ns = _arr(n_segs, np.int32)
         n_seqs = int(ns.sum())
-        if mini_off is None and mini is None:
-            n_reads, n_mini = len(bid), self._sk_n_mini
-        else:
-            mini_off = np.ascontiguousarray(mini_off, np.int64)
-            n_reads = len(mini_off) - 1
-            mini = np.ascontiguousarray(mini, np.uint64).reshape(-1, 2)
-            n_mini = len(mini)
-        bid = np.ascontiguousarray(bid, np.uint32); hash_ = np.ascontiguousarray(hash_, np.uint32)
-        qlen = None if qlen is None else np.ascontiguousarray(qlen, np.int32)
-        sl = None if seg_len is None else np.ascontiguousarray(seg_len, np.int32)
-        ref_len = np.ascontiguousarray(ref_len, np.int32)
-        cap = int(regs_cap) if regs_cap is not None else max(n_mini // 2, 1024)
-        soff = np.zeros(n_seqs + 1, np.int64); rep = np.zeros(max(n_reads, 1), np.int32)
-        regs = np.zeros(max(cap, 1), REG_DTYPE)
-        na = C.c_int64(0)
-        rc = self._lib.chaindp_map_frags(self._ctx, index, int(flag), int(max_occ), C.byref(par), int(min_cnt), C.byref(opt), n_reads, _ptr(mini_off),
-                                         _ptr(mini), _ptr(bid), _ptr(qlen), _ptr(hash_), n_seqs, _ptr(ns), _ptr(sl), _ptr(ref_len) if len(ref_len) else None,
-                                         len(ref_len), _ptr(soff), _ptr(regs), cap, _ptr(rep), C.byref(na))
-        self._n_reads, self._total = n_reads, int(na.value)
-        if rc == -2 and regs_cap is None and int(soff[-1]) > cap:              # more hits than guessed: run the post steps again with room for them
-            soff, regs = self.frag_post(opt, ref_len, ns, seg_len=sl, regs_cap=int(soff[-1]))
-        else:
-            self._check(rc)
-        return soff, regs[:int(soff[-1])], rep[:n_reads], int(na.value)
+        mini_off, mini, n_reads, n_mini = self._minimizers(mini_off, mini, bid)
+        bid, qlen, hash_ = _arr(bid, np.uint32), _arr(qlen, np.int32), _arr(hash_, np.uint32)
+        sl, ref_len = _arr(seg_len, np.int32), _arr(ref_len, np.int32)
+
+        def call(soff, regs, cap, rep, na):
+            return self._lib.chaindp_map_frags(self._ctx, index, int(flag), int(max_occ), C.byref(par), int(min_cnt), C.byref(opt), n_reads, _ptr(mini_off),
+                                               _ptr(mini), _ptr(bid), _ptr(qlen), _ptr(hash_), n_seqs, _ptr(ns), _ptr(sl), _ptr0(ref_len), len(ref_len),
+                                               _ptr(soff), _ptr(regs), cap, _ptr(rep), C.byref(na))
+        return self._hits("map_frags", regs_cap, n_seqs, call, n_reads, again=(opt, ref_len, ns, sl), n_mini=n_mini)
 
     def map_frag_seqs(self, index, w, k, is_hpc, flag, max_occ, par, min_cnt, opt, seq, seq_off, n_segs, bid, hash_, ref_len, pe_ori=-1, regs_cap=None):
         """Bases in, per-segment final hits out (chaindp_map_frag_seqs = sketch(n_segs) + map_frags()): (seg_regs_off, regs, rep_len,
         n_anchors).  pe_ori 0..3: a pair's segments are reverse-complemented on the device before the sketch and their hits flipped back
         afterwards, as the reference's worker_for does (map.c:608-631); -1 leaves the reads alone."""
         seq, seq_off = self._seqs(seq, seq_off)
-        ns = np.ascontiguousarray(n_segs, np.int32)
+        ns = _arr(n_segs, np.int32)
         n_reads, n_seqs = len(ns), len(seq_off) - 1
-        bid = np.ascontiguousarray(bid, np.uint32); hash_ = np.ascontiguousarray(hash_, np.uint32); ref_len = np.ascontiguousarray(ref_len, np.int32)
-        cap = int(regs_cap) if regs_cap is not None else max(len(seq) // 16, 1024)
-        while True:
-            soff = np.zeros(n_seqs + 1, np.int64); rep = np.zeros(max(n_reads, 1), np.int32)
-            regs = np.zeros(max(cap, 1), REG_DTYPE)
-            na = C.c_int64(0)
-            rc = self._lib.chaindp_map_frag_seqs(self._ctx, index, int(w), int(k), int(bool(is_hpc)), int(flag), int(max_occ), C.byref(par), int(min_cnt),
-                                                 C.byref(opt), int(pe_ori), n_reads, n_seqs, _ptr(ns), _ptr(seq_off), _ptr(seq) if len(seq) else None, _ptr(bid),
-                                                 _ptr(hash_), _ptr(ref_len) if len(ref_len) else None, len(ref_len), _ptr(soff), _ptr(regs), cap, _ptr(rep),
-                                                 C.byref(na))
-            self._n_reads, self._total = n_reads, int(na.value)
-            if rc == -2 and regs_cap is None and int(soff[-1]) > cap:          # more hits than guessed: the whole call again (the flip is part of it)
-                cap = int(soff[-1])
-                continue
-            self._check(rc)
-            break
-        return soff, regs[:int(soff[-1])], rep[:n_reads], int(na.value)
+        bid, hash_, ref_len = _arr(bid, np.uint32), _arr(hash_, np.uint32), _arr(ref_len, np.int32)
+
+        def call(soff, regs, cap, rep, na):
+            return self._lib.chaindp_map_frag_seqs(self._ctx, index, int(w), int(k), int(bool(is_hpc)), int(flag), int(max_occ), C.byref(par), int(min_cnt),
+                                                   C.byref(opt), int(pe_ori), n_reads, n_seqs, _ptr(ns), _ptr(seq_off), _ptr0(seq), _ptr(bid), _ptr(hash_),
+                                                   _ptr0(ref_len), len(ref_len), _ptr(soff), _ptr(regs), cap, _ptr(rep), C.byref(na))
+        return self._hits("map_frag_seqs", regs_cap, n_seqs, call, n_reads, n_bases=len(seq))
 
     def set_frag_lds_cap(self, cap=64):
         """Test hook: fragments (and segments) with more than `cap` hits (0..64) keep their work arrays in global scratch, not LDS."""
@@ -615,57 +509,41 @@ class Device:
 
     def leftover_units(self):
         """Units the two-per-wave kernel handed over to the one-per-wave kernel in the last run (test / tuning hook)."""
-        self._lib.chaindp_debug_leftover.restype = C.c_int64
-        self._lib.chaindp_debug_leftover.argtypes = [C.c_void_p]
         return int(self._lib.chaindp_debug_leftover(self._ctx))
 
     def seed_route(self):
         """How the last collect_seeds was routed (read-only test hook): dict of max_n, max_n2, lab_cap (the limits the context settled
         on when it first collected seeds), items (buckets k_seed_sort_huge handed to the LDS sort) and tied (units with equal x)."""
-        self._lib.chaindp_debug_seed_route.restype = C.c_int
-        self._lib.chaindp_debug_seed_route.argtypes = [C.c_void_p, C.c_void_p]
         out = (C.c_int64 * 5)()
         self._check(self._lib.chaindp_debug_seed_route(self._ctx, out))
         return dict(zip(("max_n", "max_n2", "lab_cap", "items", "tied"), (int(x) for x in out)))
 
     def device_bytes(self):
         """Bytes of device memory the context owns at this moment (test hook)."""
-        self._lib.chaindp_debug_device_bytes.restype = C.c_int64
-        self._lib.chaindp_debug_device_bytes.argtypes = [C.c_void_p]
         return int(self._lib.chaindp_debug_device_bytes(self._ctx))
 
     def deep_units(self):
         """Units the one-per-wave kernel handed over to k_chain_dense in the last run (test / tuning hook)."""
-        self._lib.chaindp_debug_deep_units.restype = C.c_int64
-        self._lib.chaindp_debug_deep_units.argtypes = [C.c_void_p]
         return int(self._lib.chaindp_debug_deep_units(self._ctx))
 
     def set_twin_tables(self, two=True):
         """Test hook: True keeps k_chain_twin on its layout with a cost table per half even where the batch has one table key (the
         layout with one table per wave takes such batches otherwise); False lets the device decide."""
-        self._lib.chaindp_debug_set_twin_tables.restype = C.c_int
-        self._lib.chaindp_debug_set_twin_tables.argtypes = [C.c_void_p, C.c_int]
         self._check(self._lib.chaindp_debug_set_twin_tables(self._ctx, int(bool(two))))
 
     def twin_tables(self):
         """Which layout k_chain_twin ran the last batch with (test hook): 1 one cost table per wave, 2 one per half, 0 neither."""
-        self._lib.chaindp_debug_twin_tables.restype = C.c_int
-        self._lib.chaindp_debug_twin_tables.argtypes = [C.c_void_p]
         return int(self._lib.chaindp_debug_twin_tables(self._ctx))
 
     def set_twin_handover(self, mode=0):
         """Test hook: what k_chain_twin hands over to k_chain_units whatever the units look like -- 0 nothing extra, 1 every unit
         untouched, 2 every unit after its first 64-anchor tile (k_chain_units resumes behind the flushed tiles)."""
-        self._lib.chaindp_debug_set_twin_handover.restype = C.c_int
-        self._lib.chaindp_debug_set_twin_handover.argtypes = [C.c_void_p, C.c_int]
         self._check(self._lib.chaindp_debug_set_twin_handover(self._ctx, int(mode)))
 
     def set_deep_handover(self, on=True):
         """Test hook: False keeps every unit in the launch that took it (k_chain_units then serves long scans from HBM/L2); 2 hands
         over any unit with a few deep scans, whatever its length, to k_chain_dense, 3 to k_chain_dense1, 4 to k_chain_dense16 (small
         test inputs reach every kernel)."""
-        self._lib.chaindp_debug_set_deep_handover.restype = C.c_int
-        self._lib.chaindp_debug_set_deep_handover.argtypes = [C.c_void_p, C.c_int]
         self._check(self._lib.chaindp_debug_set_deep_handover(self._ctx, on if on in (2, 3, 4) else int(bool(on))))
 
     def stats(self):

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 #include "../../include/chaindp.h"
+#include "../../include/chaindp_debug.h"
 #include "chaindp_kernels.h"
 #include "chaindp_devmem.h"
 

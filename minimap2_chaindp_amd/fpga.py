@@ -9,7 +9,7 @@ import threading
 
 import numpy as np
 
-from . import chaindp
+from . import _cabi, chaindp
 from .chaindp import SEED_DTYPE
 
 PKT_MINIMIZERS = 3        # the reference's task packets (map.c:302)
@@ -52,40 +52,10 @@ _lib = None
 
 
 def lib():
+    """chaindp.lib() with the driver ABI and this build's additions (include/chaindp_fpga.h) bound as well."""
     global _lib
     if _lib is None:
-        L = chaindp.lib()
-        vp = C.c_void_p
-        L.fpga_init.restype = C.c_int
-        L.fpga_init.argtypes = [C.c_int]
-        L.fpga_finalize.restype = None
-        L.fpga_get_retbuf.restype = vp
-        L.fpga_get_retbuf.argtypes = [C.POINTER(C.c_int), C.c_int]
-        L.fpga_release_retbuf.argtypes = [vp]
-        L.fpga_get_writebuf.restype = vp
-        L.fpga_get_writebuf.argtypes = [C.c_ulong, C.c_int]
-        L.fpga_get_writebuf_thread.restype = vp
-        L.fpga_get_writebuf_thread.argtypes = [C.c_ulong, C.c_int, C.c_int]
-        L.fpga_writebuf_submit.argtypes = [vp, C.c_uint, C.c_uint]
-        L.fpga_exit_block.restype = None
-        L.fpga_set_block.restype = None
-        L.fpga_set_params.restype = None
-        L.fpga_set_params.argtypes = [C.c_int] * 6
-        L.fpga_load_index.restype = None
-        L.fpga_load_index.argtypes = [vp, C.c_int, C.c_int]
-        L.chaindp_fpga_configure.restype = None
-        L.chaindp_fpga_configure.argtypes = [C.c_int, C.c_int, C.c_ulong]
-        L.chaindp_fpga_stats.restype = None
-        L.chaindp_fpga_stats.argtypes = [vp]
-        L.chaindp_fpga_configure_capacity.restype = None
-        L.chaindp_fpga_configure_capacity.argtypes = [C.c_int64, C.c_int64]
-        L.chaindp_fpga_configure_services.restype = None
-        L.chaindp_fpga_configure_services.argtypes = [C.c_int]
-        L.chaindp_fpga_configure_groups.restype = None
-        L.chaindp_fpga_configure_groups.argtypes = [C.c_int]
-        L.chaindp_fpga_stats_gpu.restype = C.c_int
-        L.chaindp_fpga_stats_gpu.argtypes = [C.c_int, vp]
-        _lib = L
+        _lib = _cabi.bind(chaindp.lib(), "chaindp_fpga.h")
     return _lib
 
 

@@ -4,11 +4,12 @@ GPU, and host-side helpers (generator, presets) behave."""
 import ctypes as C
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
 
-from minimap2_chaindp_amd import anchorgen as ag, chaindp, fpga, params as P
+from minimap2_chaindp_amd import _cabi, anchorgen as ag, chaindp, fpga, params as P
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -32,6 +33,80 @@ def test_library_exports_every_declared_symbol():
     L = chaindp.lib()
     assert [n for n in chaindp.ABI_SYMBOLS if getattr(L, n).argtypes is None] == []
     assert set(fpga.DRIVER_SYMBOLS) <= set(_declared("chaindp_fpga.h"))
+
+
+def test_parser_maps_declarations_by_type():
+    """_cabi.parse on declarations written here: every row of its type table, comments and preprocessor lines dropped."""
+    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
+    got = _cabi.parse("""
+        #include <stdint.h>
+        #define X_ERR (-1)   /* a macro with parentheses */
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        typedef struct { uint64_t x, y; } x_pair_t;
+        typedef struct x_ctx x_ctx_t;
+        /* a comment with a call in it: x_nothing(1); */
+        int x_count(void);
+        void x_free(void *p);   // trailing
+        x_ctx_t *x_create(int device, int64_t n, size_t bytes);
+        const char *x_error(const x_ctx_t *ctx);
+        void *x_buf(unsigned long size, unsigned int kind, uint32_t tag);
+        int x_gather(x_ctx_t *ctx, const x_pair_t *const *reads, const int32_t *n,
+                     int64_t *off /* [n_reads + 1] */);
+        int x_sizes(const x_ctx_t *ctx, size_t bytes[4], double ms[], float f, double d, int32_t k);
+        int x_run(x_ctx_t *ctx, const chaindp_params_t *par, const chaindp_post_opt_t *opt, const char *seq);
+        #ifdef __cplusplus
+        }
+        #endif
+    """)
+    assert got == {
+        "x_count": (i32, []),
+        "x_free": (None, [vp]),
+        "x_create": (vp, [i32, i64, C.c_size_t]),
+        "x_error": (C.c_char_p, [vp]),
+        "x_buf": (vp, [C.c_ulong, C.c_uint, C.c_uint]),
+        "x_gather": (i32, [vp, vp, vp, vp]),
+        "x_sizes": (i32, [vp, vp, vp, C.c_float, C.c_double, i32]),
+        "x_run": (i32, [vp, C.POINTER(P.ChainParams), C.POINTER(P.PostOpt), vp]),
+    }
+    assert list(got) == ["x_count", "x_free", "x_create", "x_error", "x_buf", "x_gather", "x_sizes", "x_run"]
+
+
+@pytest.mark.parametrize("text,named", [("int x_f(int a, long double b);", ["x_f", "long double"]), ("long double x_g(void);", ["x_g", "long double"]),
+                                        ("int x_h(int);", ["x_h"]), ("int x_k(int (*cb)(int));", ["x_k"]), ("int x_v = 3;", ["x_v"])])
+def test_parser_raises_on_what_it_does_not_understand(text, named):
+    with pytest.raises(ValueError) as e:
+        _cabi.parse(text)
+    assert all(n in str(e.value) for n in named), str(e.value)
+
+
+def _declared_params(header):
+    """{name: number of parameters} of every function a header declares, by counting commas."""
+    txt = open(os.path.join(ROOT, "include", header)).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return {n: 0 if a.strip() == "void" else a.count(",") + 1 for n, a in re.findall(r"\b((?:chaindp|fpga)_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt)}
+
+
+def test_every_declared_function_is_bound_with_its_parameter_count():
+    L = fpga.lib()
+    n_bound = 0
+    for header in ("chaindp.h", "chaindp_debug.h", "chaindp_fpga.h"):
+        counts = _declared_params(header)
+        assert sorted(counts) == _declared(header)
+        for name, n in counts.items():
+            fn = getattr(L, name)
+            assert fn.argtypes is not None and len(fn.argtypes) == n, (header, name, n, fn.argtypes)
+            n_bound += 1
+    assert n_bound == 57 + 16 + 17
+    assert chaindp.ABI_SYMBOLS == tuple(_cabi.prototypes("chaindp.h")) and all(isinstance(n, str) for n in chaindp.ABI_SYMBOLS)
+
+
+def test_debug_header_declares_exactly_the_exported_hooks():
+    nm = subprocess.run(["nm", "-D", "--defined-only", chaindp.LIB_PATH], stdout=subprocess.PIPE, text=True, check=True).stdout
+    exported = sorted(set(re.findall(r"\b(chaindp_debug_[a-z0-9_]+)$", nm, flags=re.M)))
+    assert exported == _declared("chaindp_debug.h") and len(exported) == 16
+    assert not [n for n in _declared("chaindp.h") + _declared("chaindp_fpga.h") if n.startswith("chaindp_debug_")]
 
 
 def test_driver_abi_is_the_references_eleven_symbols():

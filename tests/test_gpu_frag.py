@@ -134,8 +134,7 @@ def _seqs(frags):
 def _resident(dev, n_c, n_b):
     """What chaindp_gen_regs / chaindp_backtrack left in HBM, as it lies there: (hits, u, chain anchors)."""
     out = (np.zeros(max(n_c, 1), ol.REG_DTYPE), np.zeros(max(n_c, 1), np.uint64), np.zeros((max(n_b, 1), 2), np.uint64))
-    fn = dev._lib.chaindp_debug_bottom
-    fn.argtypes = [chaindp.C.c_void_p, chaindp.C.c_int, chaindp.C.c_void_p, chaindp.C.c_size_t]
+    fn = chaindp.lib().chaindp_debug_bottom
     for which, arr, n, size in ((7, out[0], n_c, 80), (8, out[1], n_c, 8), (9, out[2], n_b, 16)):
         if n:
             assert fn(dev._ctx, which, chaindp._ptr(arr), n * size) == 0

@@ -51,16 +51,10 @@ def test_registers_allow_the_target_waves(remarks, samegap, one):
 
 @pytest.fixture(scope="module")
 def lib():
-    import ctypes as C
     from minimap2_chaindp_amd import chaindp
     if not os.path.exists(chaindp.LIB_PATH):
         pytest.skip("library not built")
-    L = C.CDLL(chaindp.LIB_PATH)
-    L.chaindp_debug_twin_lds_bytes.restype = C.c_int64
-    L.chaindp_debug_twin_lds_bytes.argtypes = [C.c_int]
-    L.chaindp_debug_twin_max_wg_per_cu.restype = C.c_int
-    L.chaindp_debug_twin_max_wg_per_cu.argtypes = [C.c_int, C.c_int]
-    return L
+    return chaindp.lib()
 
 
 @pytest.mark.parametrize("samegap,one", sorted(TARGET_WAVES), ids=lambda x: str(x))
