@@ -305,7 +305,8 @@ int chaindp_map_seqs(chaindp_ctx_t *ctx, const chaindp_index_t *idx, int w, int 
  * segments).  chaindp_chain_post, chaindp_map_reads and chaindp_map_seqs keep refusing such batches.
  *   a read of one segment (an orphan)   exactly chaindp_chain_post's steps: the same bytes, div included
  *   a read of several segments          chain_post with mm_select_sub_multi (pe.c:6-43; its max_gap_ref is the max_dist_x of the
- *                                       chaindp_params_t the batch was run with, map.c:361-366) in the place of mm_select_sub, and
+ *                                       chaindp_params_t the batch was run with, or the read's own gap_ref where the run took per-read
+ *                                       gaps; map.c:361-366) in the place of mm_select_sub, and
  *                                       mm_join_long unless opt->flag excludes it (map.c:244); mm_seg_gen (hit.c:347-401: the hits'
  *                                       anchors split by segment, mm_gen_regs per segment with the fragment's hash and the segment's
  *                                       length, seg_split = 1, seg_id = the segment); per segment mm_set_parent and, unless
@@ -329,9 +330,9 @@ int chaindp_frag_post(chaindp_ctx_t *ctx, const chaindp_post_opt_t *opt, int64_t
 /* chaindp_map_batch (with the reads' segment counts) followed by chaindp_frag_post in one resident call: minimizers in, per-segment
  * final hits out.  Arguments as chaindp_map_reads' plus n_seqs, n_segs_per_read (required) and seg_len; mini == NULL && mini_off ==
  * NULL takes the minimizers of the last chaindp_sketch (qlen and seg_len may then be NULL too).
- * One par per call, as everywhere in this ABI: the reference derives the `sr` gaps from qlen_sum (map.c:358-366), so a caller with
- * reads of mixed lengths groups them by gap into separate calls, as fpga_shim.cpp does for its packets.  Per-read gaps are not
- * supported. */
+ * One par per call, as everywhere in this ABI.  The reference derives the `sr` gaps from qlen_sum (map.c:358-366): a caller with
+ * reads of mixed lengths either groups them by gap into separate calls, as fpga_shim.cpp does for its packets, or sets every read's
+ * own pair with chaindp_set_read_gaps (from chaindp_read_gaps) and maps them in one call. */
 int chaindp_map_frags(chaindp_ctx_t *ctx, const chaindp_index_t *idx, int flag, int max_occ, const chaindp_params_t *par, int min_cnt,
                       const chaindp_post_opt_t *opt, int64_t n_reads, const int64_t *mini_off, const chaindp_anchor_t *mini, const uint32_t *bid,
                       const int32_t *qlen, const uint32_t *hash, int64_t n_seqs, const int32_t *n_segs_per_read, const int32_t *seg_len,
@@ -424,4 +425,6 @@ int chaindp_set_variant(chaindp_ctx_t *ctx, int force_general);
 #ifdef __cplusplus
 }
 #endif
+/* per-read chaining gaps (chaindp_read_gaps, chaindp_set_read_gaps): part of this ABI, declared in a header of their own */
+#include "chaindp_gaps.h"
 #endif

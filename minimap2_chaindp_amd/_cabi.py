@@ -1,7 +1,7 @@
-"""ctypes prototypes of the C ABI, read from the headers under include/ (chaindp.h, chaindp_debug.h, chaindp_fpga.h).
+"""ctypes prototypes of the C ABI, read from the headers under include/ (chaindp.h, chaindp_gaps.h, chaindp_debug.h, chaindp_fpga.h).
 
 The headers are the one place a prototype is written down: parse() turns a header's text into {name: (restype, [argtypes])} and
-bind() sets them on the loaded library.  It reads these three headers, it is not a C parser: a declaration or a type it does not
+bind() sets them on the loaded library.  It reads these headers, it is not a C parser: a declaration or a type it does not
 know raises, nothing defaults to int."""
 import ctypes as C
 import functools

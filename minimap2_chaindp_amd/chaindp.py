@@ -5,6 +5,7 @@ kernels.  There is NO CPU implementation behind this module: a missing library o
 raises.  Per read the results equal the reference's mm_chain_dp_fpga (chain.c:218-327).
 """
 import collections
+import contextlib
 import ctypes as C
 import os
 
@@ -21,6 +22,8 @@ SEED_DTYPE = np.dtype([("x", "<u8"), ("y", "<u8"), ("p", "<i4"), ("f", "<i4")]) 
 
 # every symbol include/chaindp.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = tuple(_cabi.prototypes("chaindp.h"))
+# ... and the ones of the header it includes for per-read gaps
+GAPS_SYMBOLS = tuple(_cabi.prototypes("chaindp_gaps.h"))
 
 # chaindp_reg_t == mm_reg1_t (minimap.h:100-115), 80 bytes; `bits` is the bit-field word (rev = bit 10)
 REG_DTYPE = np.dtype([(k, "<i4") for k in ("id", "cnt", "rid", "score", "qs", "qe", "rs", "re", "parent", "subsc", "as", "mlen", "blen", "n_sub", "score0")]
@@ -35,13 +38,13 @@ _lib = None
 
 
 def lib():
-    """The library, every function of include/chaindp.h and include/chaindp_debug.h bound with the header's prototype."""
+    """The library, every function of include/chaindp.h, include/chaindp_gaps.h and include/chaindp_debug.h bound with the header's prototype."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise ChainDPError(f"{LIB_PATH} is missing: build it with __graft_entry__.build() "
                                "(make -C minimap2_chaindp_amd/csrc); there is no fallback path")
-        _lib = _cabi.bind(C.CDLL(LIB_PATH), "chaindp.h", "chaindp_debug.h")
+        _lib = _cabi.bind(C.CDLL(LIB_PATH), "chaindp.h", "chaindp_gaps.h", "chaindp_debug.h")
     return _lib
 
 
@@ -144,15 +147,44 @@ class Device:
             raise ValueError("n_segs must have one entry per read")
         return off, anchors, ns
 
+    # -- per-read chaining gaps (chaindp_set_read_gaps): read r's own (gap_ref, gap_qry) in the place of par.max_dist_x / max_dist_y
+    def set_read_gaps(self, gap_ref, gap_qry):
+        """gap_ref, gap_qry int32[n_reads] (params.read_gaps makes them): in force for every run on this context until
+        clear_read_gaps(); a batch with another number of reads is refused meanwhile."""
+        gr, gq = np.ascontiguousarray(gap_ref, np.int32), np.ascontiguousarray(gap_qry, np.int32)
+        if gr.shape != gq.shape or gr.ndim != 1:
+            raise ValueError("gap_ref and gap_qry need one entry per read each")
+        if not len(gr):
+            raise ValueError("no reads: clear_read_gaps() takes the gaps out of force")
+        self._check(self._lib.chaindp_set_read_gaps(self._ctx, len(gr), _ptr(gr), _ptr(gq)))
+
+    def clear_read_gaps(self):
+        self._check(self._lib.chaindp_set_read_gaps(self._ctx, 0, None, None))
+
+    @contextlib.contextmanager
+    def _gaps(self, gaps):
+        """What the `gaps=` keyword of the run and map calls does: gaps = (gap_ref, gap_qry) set for the call and cleared behind it,
+        None: the call as it is."""
+        if gaps is None:
+            yield
+            return
+        self.set_read_gaps(*gaps)
+        try:
+            yield
+        finally:
+            self.clear_read_gaps()
+
     # -- host-buffer path
-    def chain_batch(self, par, off, anchors, n_segs=None, want_v=True):
-        """f, p, v (int32[total]) of every read of the batch; mm_chain_dp_fpga's arrays (chain.c:246-284)."""
+    def chain_batch(self, par, off, anchors, n_segs=None, want_v=True, gaps=None):
+        """f, p, v (int32[total]) of every read of the batch; mm_chain_dp_fpga's arrays (chain.c:246-284).  gaps = (gap_ref, gap_qry)
+        int32[n_reads]: every read chained with its own gaps instead of par's (here and in every call that takes `gaps`)."""
         off, anchors, ns = self._prep(off, anchors, n_segs)
         tot = anchors.shape[0]
         f, p = np.empty(tot, np.int32), np.empty(tot, np.int32)
         v = np.empty(tot, np.int32) if want_v else None
-        self._check(self._lib.chaindp_chain_batch(self._ctx, C.byref(par), len(off) - 1, _ptr(off), _ptr(anchors), _ptr(ns),
-                                                  _ptr(f), _ptr(p), _ptr(v)))
+        with self._gaps(gaps):
+            self._check(self._lib.chaindp_chain_batch(self._ctx, C.byref(par), len(off) - 1, _ptr(off), _ptr(anchors), _ptr(ns),
+                                                      _ptr(f), _ptr(p), _ptr(v)))
         self._n_reads, self._total = len(off) - 1, tot
         return f, p, v
 
@@ -161,12 +193,14 @@ class Device:
         self._check(self._lib.chaindp_upload(self._ctx, len(off) - 1, _ptr(off), _ptr(anchors), _ptr(ns)))
         self._n_reads, self._total = len(off) - 1, anchors.shape[0]
 
-    def run(self, par):
-        self._check(self._lib.chaindp_run(self._ctx, C.byref(par)))
+    def run(self, par, gaps=None):
+        with self._gaps(gaps):
+            self._check(self._lib.chaindp_run(self._ctx, C.byref(par)))
 
-    def run_full(self, par):
+    def run_full(self, par, gaps=None):
         """run() + the compaction kernels, asynchronous, results stay in HBM (the benchmark's step)."""
-        self._check(self._lib.chaindp_run_full(self._ctx, C.byref(par)))
+        with self._gaps(gaps):
+            self._check(self._lib.chaindp_run_full(self._ctx, C.byref(par)))
 
     def sync(self):
         self._check(self._lib.chaindp_sync(self._ctx))
@@ -321,7 +355,7 @@ class Device:
             off, regs, na = np.zeros(n_off + 1, np.int64), np.zeros(max(cap, 1), REG_DTYPE), C.c_int64(0)
             rep = None if n_reads is None else np.zeros(max(n_reads, 1), np.int32)
             rc = call(off, regs, cap, rep, na)
-            if row.state == "before":
+            if row.state == "before" and (rc in (0, -2) or na.value):        # a call refused at its entry left the resident batch as it was
                 self._n_reads, self._total = n_reads, int(na.value)
             n = int(off[-1])
             short = rc == -2 and n > cap and row.retry is not None and (regs_cap is None or row.explicit == "retry")
@@ -338,7 +372,7 @@ class Device:
             self._n_reads, self._total = n_reads, int(na.value)
         return off, regs[:int(off[-1])], None if rep is None else rep[:n_reads], int(na.value)
 
-    def map_batch(self, index, flag, max_occ, par, min_cnt, mini_off, mini, bid, qlen, hash_, regs_cap=None):
+    def map_batch(self, index, flag, max_occ, par, min_cnt, mini_off, mini, bid, qlen, hash_, regs_cap=None, gaps=None):
         """Minimizers in, hits out, everything in between resident (chaindp_map_batch): (regs_off int64[n_reads+1], regs REG_DTYPE[...],
         rep_len int32[n_reads], n_anchors)."""
         mini_off, mini = _arr(mini_off, np.int64), _arr(mini, np.uint64).reshape(-1, 2)
@@ -348,7 +382,8 @@ class Device:
         def call(roff, regs, cap, rep, na):
             return self._lib.chaindp_map_batch(self._ctx, index, int(flag), int(max_occ), C.byref(par), int(min_cnt), n_reads, _ptr(mini_off), _ptr(mini),
                                                _ptr(bid), _ptr(qlen), _ptr(hash_), _ptr(roff), _ptr(regs), cap, _ptr(rep), C.byref(na))
-        return self._hits("map_batch", regs_cap, n_reads, call, n_reads, again=(hash_, qlen), n_mini=len(mini))
+        with self._gaps(gaps):
+            return self._hits("map_batch", regs_cap, n_reads, call, n_reads, again=(hash_, qlen), n_mini=len(mini))
 
     # -- chain_post + mm_est_err + mm_set_mapq (map.c:870-877, one segment, no alignment), after gen_regs() / map_batch()
     def chain_post(self, opt, ref_len, qlen=None, rep_len=None, mini_pos_off=None, mini_pos=None, regs_cap=None, want_anchors=False):
@@ -366,7 +401,7 @@ class Device:
         roff, regs, _, _ = self._hits("chain_post", regs_cap, self._n_reads, call)
         return (roff, regs, aoff, a[:int(aoff[-1])]) if want_anchors else (roff, regs)
 
-    def map_reads(self, index, flag, max_occ, par, min_cnt, opt, mini_off, mini, bid, qlen, hash_, ref_len, regs_cap=None):
+    def map_reads(self, index, flag, max_occ, par, min_cnt, opt, mini_off, mini, bid, qlen, hash_, ref_len, regs_cap=None, gaps=None):
         """Minimizers in, final hits out (chaindp_map_reads): (regs_off int64[n_reads+1], regs REG_DTYPE[...], rep_len int32[n_reads],
         n_anchors).  regs_cap None: a guess from the minimizer count, retried with the exact count if the hits need more.
         mini_off = mini = None: the minimizers the last sketch() left on the device (qlen = None then: the lengths it saw)."""
@@ -377,7 +412,8 @@ class Device:
             return self._lib.chaindp_map_reads(self._ctx, index, int(flag), int(max_occ), C.byref(par), int(min_cnt), C.byref(opt), n_reads, _ptr(mini_off),
                                                _ptr(mini), _ptr(bid), _ptr(qlen), _ptr(hash_), _ptr0(ref_len), len(ref_len), _ptr(roff), _ptr(regs), cap,
                                                _ptr(rep), C.byref(na))
-        return self._hits("map_reads", regs_cap, n_reads, call, n_reads, again=(opt, ref_len), n_mini=n_mini)
+        with self._gaps(gaps):
+            return self._hits("map_reads", regs_cap, n_reads, call, n_reads, again=(opt, ref_len), n_mini=n_mini)
 
     # -- sketch on the device: bases in, minimizers resident (chaindp_sketch)
     @staticmethod
@@ -404,7 +440,7 @@ class Device:
         self._check(self._lib.chaindp_download_minimizers(self._ctx, _ptr(m)))
         return m[:self._sk_n_mini]
 
-    def map_seqs(self, index, w, k, is_hpc, flag, max_occ, par, min_cnt, opt, seq, seq_off, bid, hash_, ref_len, regs_cap=None):
+    def map_seqs(self, index, w, k, is_hpc, flag, max_occ, par, min_cnt, opt, seq, seq_off, bid, hash_, ref_len, regs_cap=None, gaps=None):
         """Bases in, final hits out (chaindp_map_seqs = sketch() + map_reads()): (regs_off, regs, rep_len, n_anchors)."""
         seq, seq_off = self._seqs(seq, seq_off)
         n_reads = len(seq_off) - 1
@@ -414,7 +450,8 @@ class Device:
             return self._lib.chaindp_map_seqs(self._ctx, index, int(w), int(k), int(bool(is_hpc)), int(flag), int(max_occ), C.byref(par), int(min_cnt),
                                               C.byref(opt), n_reads, _ptr(seq_off), _ptr0(seq), _ptr(bid), _ptr(hash_), _ptr0(ref_len), len(ref_len),
                                               _ptr(roff), _ptr(regs), cap, _ptr(rep), C.byref(na))
-        return self._hits("map_seqs", regs_cap, n_reads, call, n_reads, again=(opt, ref_len), n_bases=len(seq))
+        with self._gaps(gaps):
+            return self._hits("map_seqs", regs_cap, n_reads, call, n_reads, again=(opt, ref_len), n_bases=len(seq))
 
     # -- reads of several segments (paired reads): chain_post with mm_select_sub_multi, mm_seg_gen, per-segment mm_set_parent / mm_set_mapq
     def frag_post(self, opt, ref_len, n_segs, seg_len=None, rep_len=None, mini_pos_off=None, mini_pos=None, regs_cap=None, want_anchors=False):
@@ -435,10 +472,10 @@ class Device:
         soff, regs, _, _ = self._hits("frag_post", regs_cap, n_seqs, call)
         return (soff, regs, aoff, a[:int(aoff[-1])]) if want_anchors else (soff, regs)
 
-    def map_frags(self, index, flag, max_occ, par, min_cnt, opt, mini_off, mini, bid, qlen, hash_, n_segs, seg_len, ref_len, regs_cap=None):
+    def map_frags(self, index, flag, max_occ, par, min_cnt, opt, mini_off, mini, bid, qlen, hash_, n_segs, seg_len, ref_len, regs_cap=None, gaps=None):
         """Minimizers in, per-segment final hits out (chaindp_map_frags): (seg_regs_off int64[n_seqs+1], regs REG_DTYPE[...], rep_len
         int32[n_reads], n_anchors).  mini_off = mini = None: the minimizers the last sketch() left on the device (qlen = seg_len = None
-        then: the lengths it saw).  One `par` per call: group reads by their gap parameters."""
+        then: the lengths it saw).  One `par` per call; reads of mixed lengths go in one call with gaps = params.read_gaps(...)."""
         ns = _arr(n_segs, np.int32)
         n_seqs = int(ns.sum())
         mini_off, mini, n_reads, n_mini = self._minimizers(mini_off, mini, bid)
@@ -449,9 +486,11 @@ class Device:
             return self._lib.chaindp_map_frags(self._ctx, index, int(flag), int(max_occ), C.byref(par), int(min_cnt), C.byref(opt), n_reads, _ptr(mini_off),
                                                _ptr(mini), _ptr(bid), _ptr(qlen), _ptr(hash_), n_seqs, _ptr(ns), _ptr(sl), _ptr0(ref_len), len(ref_len),
                                                _ptr(soff), _ptr(regs), cap, _ptr(rep), C.byref(na))
-        return self._hits("map_frags", regs_cap, n_seqs, call, n_reads, again=(opt, ref_len, ns, sl), n_mini=n_mini)
+        with self._gaps(gaps):
+            return self._hits("map_frags", regs_cap, n_seqs, call, n_reads, again=(opt, ref_len, ns, sl), n_mini=n_mini)
 
-    def map_frag_seqs(self, index, w, k, is_hpc, flag, max_occ, par, min_cnt, opt, seq, seq_off, n_segs, bid, hash_, ref_len, pe_ori=-1, regs_cap=None):
+    def map_frag_seqs(self, index, w, k, is_hpc, flag, max_occ, par, min_cnt, opt, seq, seq_off, n_segs, bid, hash_, ref_len, pe_ori=-1, regs_cap=None,
+                      gaps=None):
         """Bases in, per-segment final hits out (chaindp_map_frag_seqs = sketch(n_segs) + map_frags()): (seg_regs_off, regs, rep_len,
         n_anchors).  pe_ori 0..3: a pair's segments are reverse-complemented on the device before the sketch and their hits flipped back
         afterwards, as the reference's worker_for does (map.c:608-631); -1 leaves the reads alone."""
@@ -464,7 +503,8 @@ class Device:
             return self._lib.chaindp_map_frag_seqs(self._ctx, index, int(w), int(k), int(bool(is_hpc)), int(flag), int(max_occ), C.byref(par), int(min_cnt),
                                                    C.byref(opt), int(pe_ori), n_reads, n_seqs, _ptr(ns), _ptr(seq_off), _ptr0(seq), _ptr(bid), _ptr(hash_),
                                                    _ptr0(ref_len), len(ref_len), _ptr(soff), _ptr(regs), cap, _ptr(rep), C.byref(na))
-        return self._hits("map_frag_seqs", regs_cap, n_seqs, call, n_reads, n_bases=len(seq))
+        with self._gaps(gaps):
+            return self._hits("map_frag_seqs", regs_cap, n_seqs, call, n_reads, n_bases=len(seq))
 
     def set_frag_lds_cap(self, cap=64):
         """Test hook: fragments (and segments) with more than `cap` hits (0..64) keep their work arrays in global scratch, not LDS."""

@@ -32,7 +32,7 @@ hipError_t chaindp::dev_grow(chaindp_ctx *ctx, DevGrow &g, size_t need)
 // A new batch is resident (or, with 0 reads, none): what the calls on the one before left is no longer of this batch.
 void chaindp::begin_batch(chaindp_ctx *ctx, int64_t n_reads, int64_t total, bool mp_resident)
 {
-	ctx->n_reads = n_reads; ctx->total = total; ctx->ran = false; ctx->bot_n_reads = -1; ctx->mp_resident = mp_resident;
+	ctx->n_reads = n_reads; ctx->total = total; ctx->ran = false; ctx->ran_gaps = false; ctx->bot_n_reads = -1; ctx->mp_resident = mp_resident;
 }
 
 // the batch's per-read segment counts, if it has any, on the stream that carries its upload
@@ -79,6 +79,57 @@ int chaindp::check_params(chaindp_ctx *ctx, const chaindp_params_t *par)
 		ctx->err = "max_dist_x, max_dist_y and bw must be >= 0";
 		return CHAINDP_ERR_ARG;
 	}
+	return CHAINDP_OK;
+}
+
+// The one-call functions open with this, before anything is launched; chaindp_run checks the resident batch the same way.
+int chaindp::check_read_gaps(chaindp_ctx *ctx, int64_t n_reads)
+{
+	if (ctx->gaps_n < 0 || ctx->gaps_n == n_reads) return CHAINDP_OK;
+	ctx->err = "per-read gaps are in force for another number of reads (chaindp_set_read_gaps)";
+	return CHAINDP_ERR_ARG;
+}
+
+// map.c:358-366 for every read, in the reference's int arithmetic
+extern "C" void chaindp_read_gaps(int32_t max_gap, int32_t max_gap_ref, int32_t max_frag_len, int32_t is_sr, int64_t n_reads,
+                                  const int32_t *qlen_sum, int32_t *gap_ref, int32_t *gap_qry)
+{
+	for (int64_t r = 0; r < n_reads; ++r) {
+		const int q = qlen_sum[r];
+		int g_qry, g_ref;
+		if (is_sr) g_qry = q > max_gap ? q : max_gap;
+		else g_qry = max_gap;
+		if (max_gap_ref > 0) g_ref = max_gap_ref;
+		else if (max_frag_len > 0) {
+			g_ref = (int)((unsigned)max_frag_len - (unsigned)q);     // (the reference's int subtraction; wraps instead of overflowing)
+			if (g_ref < max_gap) g_ref = max_gap;
+		} else g_ref = max_gap;
+		if (gap_ref) gap_ref[r] = g_ref;
+		if (gap_qry) gap_qry[r] = g_qry;
+	}
+}
+
+extern "C" int chaindp_set_read_gaps(chaindp_ctx_t *ctx, int64_t n_reads, const int32_t *gap_ref, const int32_t *gap_qry)
+{
+	if (!ctx) return CHAINDP_ERR_ARG;
+	if (n_reads == 0 && !gap_ref && !gap_qry) { ctx->gaps_n = -1; return CHAINDP_OK; }      // cleared: par's gaps again
+	if (n_reads < 0 || (n_reads > 0 && (!gap_ref || !gap_qry))) { ctx->err = "chaindp_set_read_gaps: NULL gap array or negative read count"; return CHAINDP_ERR_ARG; }
+	if (n_reads > ctx->cap_reads) { ctx->err = "chaindp_set_read_gaps: more reads than the context was created for"; return CHAINDP_ERR_ARG; }
+	std::vector<int32_t> g((size_t)n_reads * 2);
+	for (int64_t r = 0; r < n_reads; ++r) {
+		if (gap_ref[r] < 0 || gap_qry[r] < 0) { ctx->err = "chaindp_set_read_gaps: gaps must be >= 0"; return CHAINDP_ERR_ARG; }   // as check_params
+		g[(size_t)r * 2] = gap_ref[r]; g[(size_t)r * 2 + 1] = gap_qry[r];
+	}
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t need = (size_t)n_reads * 8;
+	if (need > ctx->gaps_set.cap) {
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));           // a run's copy out of the old buffer may be in flight
+		HIP_TRY(ctx, dev_grow(ctx, ctx->gaps_set, need));
+	}
+	ctx->gaps_n = -1;                                              // (an error below leaves none in force)
+	if (need) HIP_TRY(ctx, hipMemcpyAsync(ctx->gaps_set.p, g.data(), need, hipMemcpyHostToDevice, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	ctx->gaps_n = n_reads;
 	return CHAINDP_OK;
 }
 
@@ -236,10 +287,11 @@ extern "C" int chaindp_set_profiling(chaindp_ctx_t *ctx, int on)
 // Launch prepass + chain DP on `st` for a batch described by device pointers, using ctx's scratch.
 static int run_on_stream(chaindp_ctx *ctx, const chaindp_params_t *par, int64_t n_reads, int64_t total,
                          const int64_t *d_off, const void *d_a, const int32_t *d_n_segs,
-                         int32_t *d_f, int32_t *d_p, int32_t *d_v, hipStream_t st)
+                         int32_t *d_f, int32_t *d_p, int32_t *d_v, hipStream_t st, bool use_gaps = false)
 {
 	int rc = check_params(ctx, par);
 	if (rc) return rc;
+	if (use_gaps && (rc = check_read_gaps(ctx, n_reads)) != CHAINDP_OK) return rc;
 	if (n_reads < 0 || total < 0) { ctx->err = "negative batch size"; return CHAINDP_ERR_ARG; }
 	if (n_reads > ctx->cap_reads || total > ctx->cap_anchors) {
 		ctx->err = "batch exceeds the capacity the context was created with";
@@ -247,9 +299,20 @@ static int run_on_stream(chaindp_ctx *ctx, const chaindp_params_t *par, int64_t 
 	}
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	const Params q = to_params(par);
+	// per-read gaps: the run keeps a copy of its own, so that setting or clearing gaps afterwards changes nothing for the stages behind it
+	const int2 *d_gaps = nullptr;
+	if (use_gaps && n_reads > 0) {
+		const size_t need = (size_t)n_reads * 8;
+		if (need > ctx->gaps_ran.cap) {
+			HIP_TRY(ctx, hipStreamSynchronize(st));
+			HIP_TRY(ctx, dev_grow(ctx, ctx->gaps_ran, need));
+		}
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->gaps_ran.p, ctx->gaps_set.p, need, hipMemcpyDeviceToDevice, st));
+		d_gaps = (const int2*)ctx->gaps_ran.p;
+	}
 	EventSet es;
 	HIP_TRY(ctx, prof_begin(ctx, es, 3, 0, st));
-	HIP_TRY(ctx, chaindp::launch_prepass(st, q, n_reads, total, d_off, d_a, ctx->d_sumq, ctx->d_units, ctx->d_counters, ctx->pre, ctx->d_unit_aux, d_n_segs, ctx->d_left_cnt));
+	HIP_TRY(ctx, chaindp::launch_prepass(st, q, n_reads, total, d_off, d_a, ctx->d_sumq, ctx->d_units, ctx->d_counters, ctx->pre, ctx->d_unit_aux, d_n_segs, ctx->d_left_cnt, d_gaps));
 	HIP_TRY(ctx, prof_mark(ctx, es, 1, st));
 	// per-read gap-cost table for the fast variant (skipped when the table would not apply)
 	uint16_t *lut = nullptr;
@@ -272,7 +335,7 @@ static int run_on_stream(chaindp_ctx *ctx, const chaindp_params_t *par, int64_t 
 	// first_child[] is initialised by the DP kernels themselves, per tile: no batch-wide memset)
 	DpBatch b;
 	b.st = st; b.par = q; b.total = total;
-	b.off = d_off; b.a = d_a; b.n_segs = d_n_segs; b.sumq = ctx->d_sumq; b.lut = lut; b.lut_stride = lut_stride;
+	b.off = d_off; b.a = d_a; b.n_segs = d_n_segs; b.gaps = d_gaps; b.sumq = ctx->d_sumq; b.lut = lut; b.lut_stride = lut_stride;
 	b.units = ctx->d_units; b.aux = ctx->d_unit_aux; b.counters = ctx->d_counters;
 	b.f = d_f; b.p = d_p; b.v = d_v; b.first_child = ctx->d_first_child; b.flags = ctx->cmp.flags; b.tg = ctx->d_tg; b.epoch = ctx->epoch;
 	b.left = ctx->d_left; b.deep = ctx->deep_handover ? ctx->d_deep : nullptr; b.hw = HandoverWords{ctx->d_left_cnt};
@@ -280,7 +343,9 @@ static int run_on_stream(chaindp_ctx *ctx, const chaindp_params_t *par, int64_t 
 	b.force_left = ctx->twin_force_left; b.two_tables = ctx->twin_two_tables; b.deep_eager = ctx->deep_eager; b.deep_route = ctx->deep_route;
 	// ordinary units two per wave (both layouts are launched, the device decides); what that kernel hands over, and nothing else,
 	// goes through k_chain_units
-	const bool twin = ctx->variant == 0 && lut;
+	// a batch with per-read gaps is k_chain_units' alone: the whole list in one launch, every unit kept to its end
+	if (d_gaps) b.deep = nullptr;
+	const bool twin = ctx->variant == 0 && lut && !d_gaps;
 	if (twin) HIP_TRY(ctx, chaindp::launch_chain_twin(ctx->dp, b));
 	HIP_TRY(ctx, chaindp::launch_chain(b, ctx->ring, twin));
 	// units whose scans kept reaching past the ring (dense repeats): redone by the dense kernels
@@ -313,8 +378,8 @@ extern "C" int chaindp_run(chaindp_ctx_t *ctx, const chaindp_params_t *par)
 {
 	if (!ctx) return CHAINDP_ERR_ARG;
 	int rc = run_on_stream(ctx, par, ctx->n_reads, ctx->total, ctx->d_off, ctx->d_a, ctx->has_n_segs ? ctx->d_n_segs : nullptr,
-	                       ctx->d_f, ctx->d_p, ctx->d_v, ctx->stream);
-	if (rc == CHAINDP_OK) { ctx->ran = true; ctx->singles_pending = true; ctx->ran_par = *par; }
+	                       ctx->d_f, ctx->d_p, ctx->d_v, ctx->stream, ctx->gaps_n >= 0);
+	if (rc == CHAINDP_OK) { ctx->ran = true; ctx->singles_pending = true; ctx->ran_par = *par; ctx->ran_gaps = ctx->gaps_n >= 0 && ctx->n_reads > 0; }
 	return rc;
 }
 
@@ -324,6 +389,7 @@ extern "C" int chaindp_run_device(chaindp_ctx_t *ctx, const chaindp_params_t *pa
 {
 	if (!ctx) return CHAINDP_ERR_ARG;
 	if (!d_off || (total_anchors > 0 && (!d_a || !d_f || !d_p || !d_v))) { ctx->err = "NULL device pointer"; return CHAINDP_ERR_ARG; }
+	if (ctx->gaps_n >= 0) { ctx->err = "chaindp_run_device takes no per-read gaps: clear them (the batch is the caller's)"; return CHAINDP_ERR_ARG; }
 	hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
 	const int rc = run_on_stream(ctx, par, n_reads, total_anchors, (const int64_t*)d_off, d_a, (const int32_t*)d_n_segs,
 	                             (int32_t*)d_f, (int32_t*)d_p, (int32_t*)d_v, st);
@@ -367,6 +433,7 @@ extern "C" int chaindp_chain_batch(chaindp_ctx_t *ctx, const chaindp_params_t *p
 	if (!ctx) return CHAINDP_ERR_ARG;
 	int rc = check_params(ctx, par);
 	if (rc) return rc;
+	if ((rc = check_read_gaps(ctx, n_reads)) != CHAINDP_OK) return rc;
 	if ((rc = chaindp_upload(ctx, n_reads, off, a, n_segs_per_read)) != CHAINDP_OK) return rc;
 	if ((rc = chaindp_run(ctx, par)) != CHAINDP_OK) return rc;
 	return chaindp_download(ctx, f, p, v);

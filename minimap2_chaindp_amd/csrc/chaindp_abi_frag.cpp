@@ -87,11 +87,13 @@ static int frag_post_impl(chaindp_ctx *ctx, const chaindp_post_opt_t *opt, int64
 	if ((rc = post_stage_rep_len(ctx, rep_len, R, &d_rep)) != CHAINDP_OK) return rc;
 	HIP_TRY(ctx, hipMemsetAsync(ctx->d_post_err, 0, 4, st));
 	const chaindp::PostOpt po = to_post_opt(opt);
+	// mm_select_sub_multi's max_gap_ref (map.c:243) is the gap_ref the read was chained with: the run's own copy where it took per-read gaps
+	const int2 *d_read_gaps = ctx->ran_gaps ? (const int2*)ctx->gaps_ran.p : nullptr;
 	// chain_post per read and the first half of mm_seg_gen.  The global scratch of what exceeds the LDS cap is sized for the fragments'
 	// hits at this point and grown below for the segments' hits, once their count is known.
 	HIP_TRY(ctx, chaindp::launch_frag_read(st, R, ctx->bot.chains_off, ctx->bot.b_off, ctx->bot.b_out, ctx->regs.p, ctx->d_rqlen, d_read_seq0, d_seq_len, po,
 	                                       ctx->ran_par.max_dist_x, ctx->frag_lds_cap, (int32_t*)ctx->post_scratch.p, ctx->post_stage.p, ctx->post_sq.p,
-	                                       ctx->d_post_off, d_g, d_o, d_a));
+	                                       ctx->d_post_off, d_g, d_o, d_a, d_read_gaps));
 	HIP_TRY(ctx, chaindp::launch_scan_u64(st, R, ctx->d_post_off, ctx->d_post_tile, ctx->d_post_off + R));
 	HIP_TRY(ctx, chaindp::launch_scan_u64(st, S, d_g, d_tile, d_g + S));
 	HIP_TRY(ctx, chaindp::launch_scan_u64(st, S, d_o, d_tile, d_o + S));
@@ -157,6 +159,7 @@ static int map_frags_impl(chaindp_ctx *ctx, const chaindp_index_t *ix, int flag,
 	if (!ctx) return CHAINDP_ERR_ARG;
 	int rc = check_params(ctx, par);
 	if (rc) return rc;
+	if ((rc = check_read_gaps(ctx, n_reads)) != CHAINDP_OK) return rc;
 	if (!opt || !seg_regs_off || regs_cap < 0 || (regs_cap > 0 && !regs) || (n_reads > 0 && (!hash || !n_segs_per_read))) {
 		ctx->err = "NULL output, hash, n_segs_per_read or opt"; return CHAINDP_ERR_ARG;
 	}
@@ -186,6 +189,7 @@ extern "C" int chaindp_map_frag_seqs(chaindp_ctx_t *ctx, const chaindp_index_t *
 	if (!ctx) return CHAINDP_ERR_ARG;
 	int rc = check_params(ctx, par);
 	if (rc) return rc;
+	if ((rc = check_read_gaps(ctx, n_reads)) != CHAINDP_OK) return rc;
 	if (!opt || !seg_regs_off || regs_cap < 0 || (regs_cap > 0 && !regs) || (n_reads > 0 && (!hash || !bid || !n_segs_per_read))) {
 		ctx->err = "NULL output, bid, hash, n_segs_per_read or opt"; return CHAINDP_ERR_ARG;
 	}

@@ -205,6 +205,7 @@ extern "C" int chaindp_map_reads(chaindp_ctx_t *ctx, const chaindp_index_t *ix, 
 	if (!ctx) return CHAINDP_ERR_ARG;
 	int rc = check_params(ctx, par);
 	if (rc) return rc;
+	if ((rc = check_read_gaps(ctx, n_reads)) != CHAINDP_OK) return rc;
 	if (!opt || !regs_off || regs_cap < 0 || (regs_cap > 0 && !regs) || (n_reads > 0 && !hash)) { ctx->err = "NULL output, hash or opt"; return CHAINDP_ERR_ARG; }
 	if (par->n_segs > 1) { ctx->err = "chaindp_map_reads takes single-segment reads only (n_segs > 1)"; return CHAINDP_ERR_ARG; }
 	// the stages of chaindp_map_batch, with the hits left in HBM, then chain_post on them
@@ -221,6 +222,7 @@ extern "C" int chaindp_map_seqs(chaindp_ctx_t *ctx, const chaindp_index_t *ix, i
 	if (!ctx) return CHAINDP_ERR_ARG;
 	int rc = check_params(ctx, par);
 	if (rc) return rc;
+	if ((rc = check_read_gaps(ctx, n_reads)) != CHAINDP_OK) return rc;
 	if (!opt || !regs_off || regs_cap < 0 || (regs_cap > 0 && !regs) || (n_reads > 0 && (!hash || !bid))) { ctx->err = "NULL output, bid, hash or opt"; return CHAINDP_ERR_ARG; }
 	if (!ix || ix->device != ctx->device) { ctx->err = "index image missing or on another device"; return CHAINDP_ERR_ARG; }
 	std::vector<int64_t> mini_off((size_t)(n_reads > 0 ? n_reads + 1 : 1));

@@ -199,6 +199,7 @@ extern "C" int chaindp_map_batch(chaindp_ctx_t *ctx, const chaindp_index_t *ix, 
 	if (!ctx) return CHAINDP_ERR_ARG;
 	int rc = check_params(ctx, par);
 	if (rc) return rc;
+	if ((rc = check_read_gaps(ctx, n_reads)) != CHAINDP_OK) return rc;
 	if (!regs_off || regs_cap < 0 || (regs_cap > 0 && !regs) || (n_reads > 0 && !hash)) { ctx->err = "NULL output or hash"; return CHAINDP_ERR_ARG; }
 	return map_prefix(ctx, ix, flag, max_occ, par, min_cnt, n_reads, mini_off, mini, bid, qlen, nullptr, hash, rep_len, n_anchors, regs_off, regs, regs_cap);
 }

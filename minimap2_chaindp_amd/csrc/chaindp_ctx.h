@@ -27,6 +27,11 @@ struct chaindp_ctx {
 	bool has_n_segs = false, ran = false;
 	bool singles_pending = false;    // the last run left f, p, v, flags[] of its singletons to k_fill_singles (chaindp_download runs it)
 	chaindp_params_t ran_par{};      // the parameters of that run
+	// per-read chaining gaps (chaindp_set_read_gaps): int2 (gap_ref, gap_qry) per read
+	chaindp::DevGrow gaps_set;       // the gaps in force, for gaps_n reads
+	chaindp::DevGrow gaps_ran;       // the last run's own copy of them: what the stages behind that run read
+	int64_t gaps_n = -1;             // reads the gaps in force were set for; -1: none are in force
+	bool ran_gaps = false;           // the last run took its gaps from gaps_ran instead of ran_par.max_dist_x / max_dist_y
 	int64_t *d_off = nullptr;
 	void *d_a = nullptr;
 	int32_t *d_n_segs = nullptr;
@@ -148,6 +153,7 @@ hipError_t prof_begin(chaindp_ctx *ctx, EventSet &es, int n, int slot0, hipStrea
 hipError_t prof_mark(chaindp_ctx *ctx, EventSet &es, int k, hipStream_t st);
 Params to_params(const chaindp_params_t *p);
 int check_params(chaindp_ctx *ctx, const chaindp_params_t *par);
+int check_read_gaps(chaindp_ctx *ctx, int64_t n_reads);   // ERR_ARG while per-read gaps are in force for another number of reads
 int check_batch(const chaindp_ctx *ctx, int64_t n_reads, const int64_t *off, const void *payload, bool per_read, const char *owner,
                 std::string &err, int64_t &total);
 int stage_pointers(chaindp_ctx *ctx, const void *const *ptrs, int64_t n);

@@ -137,11 +137,13 @@ __global__ __launch_bounds__(64) void k_frag_read(int64_t n_reads, const int64_t
                                                   const int32_t *__restrict__ read_seq0, const int32_t *__restrict__ seq_len, PostOpt o, int max_gap_ref,
                                                   int lds_cap, int32_t *__restrict__ scratch, int32_t *__restrict__ stage, ulonglong2 *__restrict__ sq,
                                                   unsigned long long *__restrict__ n_out, unsigned long long *__restrict__ cnt_g,
-                                                  unsigned long long *__restrict__ cnt_o, unsigned long long *__restrict__ cnt_a)
+                                                  unsigned long long *__restrict__ cnt_o, unsigned long long *__restrict__ cnt_a,
+                                                  const int2 *__restrict__ read_gaps)
 {
 	__shared__ int lds[PF_NF * FRAG_LDS_CAP];
 	const int64_t r = blockIdx.x;
 	if (r >= n_reads) return;
+	if (read_gaps) max_gap_ref = read_gaps[r].x;                         // the run's own gap_ref of read r (chaindp_set_read_gaps)
 	const int64_t n = chains_off[r + 1] - chains_off[r];
 	if (n <= lds_cap) frag_read<true>(r, chains_off, b_off, b, regs, qlen, read_seq0, seq_len, o, max_gap_ref, scratch, stage, sq, n_out, cnt_g, cnt_o, cnt_a, lds);
 	else frag_read<false>(r, chains_off, b_off, b, regs, qlen, read_seq0, seq_len, o, max_gap_ref, scratch, stage, sq, n_out, cnt_g, cnt_o, cnt_a, lds);
@@ -312,13 +314,13 @@ __global__ __launch_bounds__(256) void k_frag_flip(int64_t n_seqs, const int32_t
 hipError_t launch_frag_read(hipStream_t st, int64_t n_reads, const int64_t *d_chains_off, const int64_t *d_b_off, const void *d_b, const void *d_regs,
                             const int32_t *d_qlen, const int32_t *d_read_seq0, const int32_t *d_seq_len, const PostOpt &o, int max_gap_ref, int lds_cap,
                             int32_t *d_scratch, void *d_stage, void *d_sq, unsigned long long *d_n_out, unsigned long long *d_cnt_g,
-                            unsigned long long *d_cnt_o, unsigned long long *d_cnt_a)
+                            unsigned long long *d_cnt_o, unsigned long long *d_cnt_a, const int2 *d_read_gaps)
 {
 	if (n_reads <= 0) return hipSuccess;
 	if (lds_cap > FRAG_LDS_CAP || lds_cap < 0) lds_cap = FRAG_LDS_CAP;
 	hipLaunchKernelGGL(k_frag_read, dim3((unsigned)n_reads), dim3(64), 0, st, n_reads, d_chains_off, d_b_off, (const ulonglong2*)d_b,
 	                   (const int32_t*)d_regs, d_qlen, d_read_seq0, d_seq_len, o, max_gap_ref, lds_cap, d_scratch, (int32_t*)d_stage, (ulonglong2*)d_sq,
-	                   d_n_out, d_cnt_g, d_cnt_o, d_cnt_a);
+	                   d_n_out, d_cnt_g, d_cnt_o, d_cnt_a, d_read_gaps);
 	return hipGetLastError();
 }
 

@@ -49,7 +49,8 @@ size_t prepass_scratch_bytes(int64_t max_anchors, size_t *mask_bytes, size_t *bl
 // d_left_cnt: the four hand-over words (HandoverWords, below), zeroed with the batch's other accumulators
 hipError_t launch_prepass(hipStream_t st, const Params &par, int64_t n_reads, int64_t total, const int64_t *d_off, const void *d_a,
                           unsigned long long *d_sumq, Unit *d_units, unsigned long long *d_counters, PrepassScratch sc,
-                          UnitAux *d_unit_aux, const int32_t *d_n_segs, unsigned long long *d_left_cnt);
+                          UnitAux *d_unit_aux, const int32_t *d_n_segs, unsigned long long *d_left_cnt, const int2 *d_gaps = nullptr);
+// (d_gaps: per read (gap_ref, gap_qry); units are then cut with the gap_ref of the read each anchor lies in instead of par.max_dist_x)
 // f, p, v, flags[] of the batch's singletons (the prepass only marks them; the compaction reads the marks)
 hipError_t launch_fill_singles(hipStream_t st, const Params &par, int64_t total, const void *d_a, PrepassScratch sc,
                                int32_t *d_f, int32_t *d_p, int32_t *d_v, uint8_t *d_flags);
@@ -91,6 +92,8 @@ struct DpBatch {
 	const int64_t *off;
 	const void *a;
 	const int32_t *n_segs;               // per read, or nullptr: par.n_segs for all
+	const int2 *gaps;                    // per read (gap_ref, gap_qry) in the place of par.max_dist_x / max_dist_y, or nullptr: par's for all.
+	                                     // A gap batch is k_chain_units' alone: no k_chain_twin, deep == nullptr
 	const unsigned long long *sumq;
 	const uint16_t *lut;                 // nullptr: no tables, every unit takes the general variant
 	int lut_stride;
@@ -129,9 +132,9 @@ size_t twin_stamp_bytes(int cus);
 // dynamic segment; max_lds is the most dynamic LDS a launch can ask it for.  chaindp_create checks the one and provides for the
 // other, once per context; every *_kernels() below lists the instantiations of one source file into out[] and returns their number.
 struct DpKernel { const void *fn; const char *name; size_t max_lds; };
-#define CHAINDP_DP_KERNELS 13
+#define CHAINDP_DP_KERNELS 16
 int twin_kernels(DpKernel *out);      // 4
-int units_kernels(DpKernel *out);     // 3
+int units_kernels(DpKernel *out);     // 6: three rings, each with the batch's gaps and with per-read gaps
 int dense_kernels(DpKernel *out);     // 2
 int dense16_kernels(DpKernel *out);   // 2
 int dense1_kernels(DpKernel *out);    // 2
@@ -233,7 +236,7 @@ hipError_t launch_post_logf_probe(hipStream_t st, int kmax, const uint32_t *d_pk
 hipError_t launch_frag_read(hipStream_t st, int64_t n_reads, const int64_t *d_chains_off, const int64_t *d_b_off, const void *d_b, const void *d_regs,
                             const int32_t *d_qlen, const int32_t *d_read_seq0, const int32_t *d_seq_len, const PostOpt &o, int max_gap_ref, int lds_cap,
                             int32_t *d_scratch, void *d_stage, void *d_sq, unsigned long long *d_n_out, unsigned long long *d_cnt_g,
-                            unsigned long long *d_cnt_o, unsigned long long *d_cnt_a);
+                            unsigned long long *d_cnt_o, unsigned long long *d_cnt_a, const int2 *d_read_gaps = nullptr);   // d_read_gaps[r].x replaces max_gap_ref
 hipError_t launch_frag_split(hipStream_t st, int64_t n_reads, const unsigned long long *d_post_off, const void *d_post_out, const int64_t *d_b_off,
                              const void *d_sq, const int32_t *d_read_seq0, const int32_t *d_seq_len, const uint32_t *d_hash, const int32_t *d_rep_len,
                              const unsigned long long *d_g_off, const unsigned long long *d_o_off, const unsigned long long *d_a_off,

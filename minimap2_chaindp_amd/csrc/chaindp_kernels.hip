@@ -563,7 +563,10 @@ __device__ __forceinline__ void run_unit_fast(const UnitCtx &c, int64_t room, in
 	}
 }
 
-template <int RING>
+// GAPS: the batch carries one (gap_ref, gap_qry) pair per read (gaps[read], chaindp_set_read_gaps) and every unit takes its read's pair in
+// the place of par.max_dist_x / max_dist_y: the window, the filters, whether 32-bit differences are exact and which variant runs are
+// settled per unit.  Such a launch keeps every unit to its end (nothing is handed to the dense kernels, whose gaps are per batch).
+template <int RING, bool GAPS = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_chain_units(Params par, const int64_t *__restrict__ off,
                                                     const ulonglong2 *__restrict__ a, const int32_t *__restrict__ n_segs_pr,
                                                     const unsigned long long *__restrict__ sumq,
@@ -573,7 +576,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                                                     int32_t *f, int32_t *p, int32_t *v, unsigned long long *tg, uint32_t epoch,
                                                     int32_t *first_child, uint8_t *flags,
                                                     const Unit *__restrict__ units_all, const unsigned long long *__restrict__ counters_all,
-                                                    Unit *deep_list, unsigned int *deep_cnt, const unsigned int *__restrict__ long_units, int deep_eager, int deep_route)
+                                                    Unit *deep_list, unsigned int *deep_cnt, const unsigned int *__restrict__ long_units, int deep_eager, int deep_route,
+                                                    const int2 *__restrict__ gaps)
 {
 	static_assert((RING & (RING - 1)) == 0 && RING >= 128, "RING must be a power of two >= 128");
 	extern __shared__ uint4 smem[];
@@ -589,7 +593,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 	c.s_lut = s_lut;
 	c.lane = threadIdx.x;
 	// k_chain_dense keeps 32-bit differences over a ring of CHAINDP_DENSE_RING anchors: exact under the same condition as x32_ok below
-	c.deep_list = ((uint64_t)(int64_t)par.max_dist_x + 1) * (uint64_t)(CHAINDP_DENSE_RING + 1) < (1ull << 32) ? deep_list : nullptr;
+	c.deep_list = !GAPS && ((uint64_t)(int64_t)par.max_dist_x + 1) * (uint64_t)(CHAINDP_DENSE_RING + 1) < (1ull << 32) ? deep_list : nullptr;
 	// Which kernel takes them depends on the batch: with a few long units it has a tail, and k_chain_dense puts eight waves on each
 	// of the first CHAINDP_DENSE_UNITS handed over (units run longest first); with thousands of them (*long_units: units of 8192
 	// anchors and more, from the prepass' length classes) every SIMD is busy to the end, the batch is bound by what a pair evaluation
@@ -602,7 +606,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 	c.mdq = par.max_dist_x < par.max_dist_y ? par.max_dist_x : par.max_dist_y;   // dq > max_dist_y || dq > max_dist_x (same segment)
 	// 32-bit differences are exact while (RING + 1) * max_dist_x + 2 < 2^32: consecutive anchors of a unit are at
 	// most max_dist_x apart, the ring spans RING of them, and unwritten slots sit max_dist_x + 2 below the unit start
-	const bool x32_ok = ((uint64_t)(int64_t)par.max_dist_x + 1) * (uint64_t)(RING + 1) < (1ull << 32);
+	bool x32_ok = ((uint64_t)(int64_t)par.max_dist_x + 1) * (uint64_t)(RING + 1) < (1ull << 32);
+	int mdx = par.max_dist_x, mdy = par.max_dist_y;                // the gaps of the unit in hand (GAPS: its read's own)
 	const int lane = threadIdx.x;
 
 	int64_t n_units = (int64_t)(uint32_t)counters[0];             // low word: units, high word: singletons (prepass)
@@ -622,8 +627,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 		c.rel0 = (int)(u.start - rs);
 		c.avgd = (double)((float)(uint64_t)(sq & ~SUMQ_FLAGS) / (float)(int64_t)(re - rs));   // chain.c:241: f32 divide of converted u64 and i64
 		c.seg_rule = n_segs > 1 && !par.is_cdna;                   // chain.c:261
+		if constexpr (GAPS) {
+			const int2 g = gaps[u.read];
+			mdx = g.x; mdy = g.y;
+			c.maxx = (uint64_t)(int64_t)mdx; c.mdx = mdx; c.mdy = mdy; c.mdq = mdx < mdy ? mdx : mdy;
+			x32_ok = ((uint64_t)(int64_t)mdx + 1) * (uint64_t)(RING + 1) < (1ull << 32);
+		}
 		const bool general = par.is_cdna || n_segs > 1 || (sq & SUMQ_SEG_FLAG) || lut == nullptr || !x32_ok
-		                     || par.max_dist_x < 1 || par.max_dist_y < 0;
+		                     || mdx < 1 || mdy < 0;
 
 		wave_mem_fence();
 		for (int k = lane; k < RING; k += 64) c.s_t[k] = -1;
@@ -637,7 +648,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 		wave_mem_fence();
 		// u.len bounds the unit (next unit's start or the read's end); run_unit finds the true end at the first gap
 		if (general) run_unit<RING>(c, (int64_t)u.len);
-		else if (par.max_dist_y >= par.max_dist_x) run_unit_fast<RING, true>(c, (int64_t)u.len, resume);
+		else if (mdy >= mdx) run_unit_fast<RING, true>(c, (int64_t)u.len, resume);
 		else run_unit_fast<RING, false>(c, (int64_t)u.len, resume);
 	}
 }
@@ -650,6 +661,7 @@ size_t chain_lds_bytes(int ring, int lut_stride)
 }
 hipError_t launch_chain(const DpBatch &b, int ring, bool leftovers)
 {
+	if (b.gaps && leftovers) return hipErrorInvalidValue;         // a gap batch goes through this kernel alone, as one list
 	// The number of units is only known on the device (counters[0]); the grid is sized for the upper
 	// bound and blocks beyond the count exit at once, so no host round trip sits between the kernels.
 	int64_t blocks = b.total / 2;
@@ -660,12 +672,13 @@ hipError_t launch_chain(const DpBatch &b, int ring, bool leftovers)
 	auto kernel = k_chain_units<128>;
 	if (ring == 512) kernel = k_chain_units<512>;
 	else if (ring != 128) kernel = k_chain_units<256>;
+	if (b.gaps) kernel = ring == 512 ? k_chain_units<512, true> : ring != 128 ? k_chain_units<256, true> : k_chain_units<128, true>;
 	// the leftover list's count is the hand-over word; all ones there send the kernel to the whole list (units_all, counters_all)
 	hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), lds, b.st, b.par, b.off, (const ulonglong2*)b.a, b.n_segs, b.sumq, b.lut, b.lut_stride,
 	                   leftovers ? (const Unit*)b.left : b.units, leftovers ? (const unsigned long long*)b.hw.left_word() : b.counters,
 	                   b.f, b.p, b.v, b.tg, b.epoch, b.first_child, b.flags,
 	                   leftovers ? b.units : (const Unit*)nullptr, leftovers ? b.counters : (const unsigned long long*)nullptr,
-	                   b.deep, b.hw.deep_count(), b.long_units, b.deep_eager, b.deep_route);
+	                   b.deep, b.hw.deep_count(), b.long_units, b.deep_eager, b.deep_route, b.gaps);
 	return hipGetLastError();
 }
 
@@ -674,7 +687,10 @@ int units_kernels(DpKernel *out)
 	out[0] = {(const void*)k_chain_units<128>, "k_chain_units<128>", chain_lds_bytes(128, CHAINDP_LUT_MAX_STRIDE)};
 	out[1] = {(const void*)k_chain_units<256>, "k_chain_units<256>", chain_lds_bytes(256, CHAINDP_LUT_MAX_STRIDE)};
 	out[2] = {(const void*)k_chain_units<512>, "k_chain_units<512>", chain_lds_bytes(512, CHAINDP_LUT_MAX_STRIDE)};
-	return 3;
+	out[3] = {(const void*)k_chain_units<128, true>, "k_chain_units<128, gaps>", chain_lds_bytes(128, CHAINDP_LUT_MAX_STRIDE)};
+	out[4] = {(const void*)k_chain_units<256, true>, "k_chain_units<256, gaps>", chain_lds_bytes(256, CHAINDP_LUT_MAX_STRIDE)};
+	out[5] = {(const void*)k_chain_units<512, true>, "k_chain_units<512, gaps>", chain_lds_bytes(512, CHAINDP_LUT_MAX_STRIDE)};
+	return 6;
 }
 
 } // namespace chaindp

@@ -97,12 +97,16 @@ __device__ __forceinline__ void pw_wait(pw_u32x4 &q0, pw_u32x4 &q1)     // both 
 #endif
 }
 
-template <bool FULL>                                                 // FULL: all 1024 anchors exist (every block but the batch's last)
+// GAPS: units are cut with the gap_ref of the read each anchor lies in (gaps[read].x, chaindp_set_read_gaps) instead of par.max_dist_x:
+// every lane range of a tile leaves its read's gap in its lanes and the two distance tests are made per lane, behind the ranges.  An
+// anchor and the neighbour it is measured against lie in one read wherever the test counts: the read's bounds force the rest.
+template <bool FULL, bool GAPS = false>                              // FULL: all 1024 anchors exist (every block but the batch's last)
 __device__ __forceinline__ void prepass_block(const Params &par, const int64_t b, const int lane, const int64_t total,
                                               const int64_t *__restrict__ off, const ulonglong2 *__restrict__ a,
                                               unsigned long long *__restrict__ sumq, uint64_t *__restrict__ start_mask,
                                               uint64_t *__restrict__ single_mask, uint64_t *__restrict__ emit_mask,
-                                              unsigned long long *__restrict__ block_cnt, const int2 *__restrict__ block_reads)
+                                              unsigned long long *__restrict__ block_cnt, const int2 *__restrict__ block_reads,
+                                              const int2 *__restrict__ gaps = nullptr)
 {
 	const uint64_t maxx = (uint64_t)(int64_t)par.max_dist_x;
 	const int64_t g0 = b * PRE_PER_BLOCK;
@@ -177,7 +181,9 @@ __device__ __forceinline__ void prepass_block(const Params &par, const int64_t b
 		const int span = (int)(an.w & 0xffu);
 		const uint32_t segbits = an.w & 0x00ff0000u;
 		// lane masks, combined by the scalar unit
-		const uint64_t far_prev = __builtin_amdgcn_uicmpl(x - xprev, maxx, 34), far_next = __builtin_amdgcn_uicmpl(xnext - x, maxx, 34);
+		uint64_t far_prev = 0, far_next = 0;
+		if constexpr (!GAPS) { far_prev = __builtin_amdgcn_uicmpl(x - xprev, maxx, 34); far_next = __builtin_amdgcn_uicmpl(xnext - x, maxx, 34); }
+		uint32_t gap_l = 0;                                          // GAPS: the gap_ref of this lane's read
 		const uint64_t zero_m = __builtin_amdgcn_uicmp((unsigned)span, 0u, 32) & have_m;
 		// the reads of the tile, one lane range after the other (usually one: the whole tile inside r_cur)
 		uint64_t start_x = 0, last_x = 0;                            // starts / ends forced by the reads' bounds
@@ -192,16 +198,21 @@ __device__ __forceinline__ void prepass_block(const Params &par, const int64_t b
 			const int l_re = re_b - tb;                              // r_cur ends in front of this lane of the tile (> seg_lo)
 			const int seg_hi = l_re < in_tile ? l_re : in_tile;
 			if (l_re <= 64) last_x |= 1ull << (l_re - 1);
+			uint32_t gap_r = 0;
+			if constexpr (GAPS) gap_r = (uint32_t)*TW_CONST(int32_t, &gaps[r_cur].x);
 			if (seg_lo == 0 && seg_hi == 64) {
 				w_sum += (unsigned int)span; any_seg |= segbits; span0_m |= zero_m;
+				if constexpr (GAPS) gap_l = gap_r;
 			} else {                                                 // lanes [seg_lo, seg_hi) are r_cur's
 				const uint64_t m = ((seg_hi == 64 ? 0ull : 1ull << seg_hi) - 1ull) & (~0ull << seg_lo);
 				const bool mine = __builtin_amdgcn_inverse_ballot_w64(m);
 				w_sum += mine ? (unsigned int)span : 0u; any_seg |= mine ? segbits : 0u; span0_m |= zero_m & m;
+				if constexpr (GAPS) gap_l = mine ? gap_r : gap_l;
 			}
 			if (seg_hi >= in_tile) break;
 			seg_lo = seg_hi;
 		}
+		if constexpr (GAPS) { far_prev = __builtin_amdgcn_uicmpl(x - xprev, (uint64_t)gap_l, 34); far_next = __builtin_amdgcn_uicmpl(xnext - x, (uint64_t)gap_l, 34); }
 		const uint64_t start_m = (far_prev | start_x) & have_m;
 		const uint64_t single_m = start_m & (far_next | last_x);
 		// a singleton's results (chain.c:251,283-284 with an empty window: f = v = q_span, p = -1; emitted at its own step iff
@@ -249,6 +260,22 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_prepass(Params par, int64_t n_rea
 	if (g0 >= total) return;
 	if (g0 + PRE_PER_BLOCK <= total) prepass_block<true>(par, b, lane, total, off, a, sumq, start_mask, single_mask, emit_mask, block_cnt, block_reads);
 	else prepass_block<false>(par, b, lane, total, off, a, sumq, start_mask, single_mask, emit_mask, block_cnt, block_reads);
+}
+
+// the same with per-read gaps (prepass_block<.., true>)
+__global__ __launch_bounds__(PRE_BLOCK) void k_prepass_gaps(Params par, int64_t n_reads, int64_t total,
+                                                            const int64_t *__restrict__ off, const ulonglong2 *__restrict__ a,
+                                                            unsigned long long *__restrict__ sumq, uint64_t *__restrict__ start_mask,
+                                                            uint64_t *__restrict__ single_mask, uint64_t *__restrict__ emit_mask,
+                                                            unsigned long long *__restrict__ block_cnt, const int2 *__restrict__ block_reads,
+                                                            const int2 *__restrict__ gaps)
+{
+	const int lane = threadIdx.x & 63;
+	const int64_t b = (int64_t)blockIdx.x * (PRE_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	const int64_t g0 = b * PRE_PER_BLOCK;
+	if (g0 >= total) return;
+	if (g0 + PRE_PER_BLOCK <= total) prepass_block<true, true>(par, b, lane, total, off, a, sumq, start_mask, single_mask, emit_mask, block_cnt, block_reads, gaps);
+	else prepass_block<false, true>(par, b, lane, total, off, a, sumq, start_mask, single_mask, emit_mask, block_cnt, block_reads, gaps);
 }
 
 // f, p, v and flags[] of the singletons, from the prepass' masks: for callers that read those arrays (chaindp_download, a run on the
@@ -443,7 +470,7 @@ __global__ __launch_bounds__(256) void k_build_lut(Params par, int64_t n_reads, 
 
 hipError_t launch_prepass(hipStream_t st, const Params &par, int64_t n_reads, int64_t total, const int64_t *d_off, const void *d_a,
                           unsigned long long *d_sumq, Unit *d_units, unsigned long long *d_counters, PrepassScratch sc,
-                          UnitAux *d_unit_aux, const int32_t *d_n_segs, unsigned long long *d_left_cnt)
+                          UnitAux *d_unit_aux, const int32_t *d_n_segs, unsigned long long *d_left_cnt, const int2 *d_gaps)
 {
 	hipError_t e = hipSuccess;
 	if (n_reads <= 0 || total <= 0) {                                // an empty batch: no units, no singletons, nothing handed over
@@ -454,8 +481,12 @@ hipError_t launch_prepass(hipStream_t st, const Params &par, int64_t n_reads, in
 	const int64_t words = (total + 63) / 64;
 	hipLaunchKernelGGL(k_block_reads, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, n_reads, total, d_off, sc.block_reads,
 	                   d_sumq, d_counters, sc.hist, d_left_cnt);
-	hipLaunchKernelGGL(k_prepass, dim3((unsigned)((blocks + PRE_BLOCK / 64 - 1) / (PRE_BLOCK / 64))), dim3(PRE_BLOCK), 0, st, par, n_reads, total, d_off, (const ulonglong2*)d_a,
-	                   d_sumq, sc.start_mask, sc.single_mask, sc.emit_mask, sc.block_cnt, sc.block_reads);
+	if (d_gaps)
+		hipLaunchKernelGGL(k_prepass_gaps, dim3((unsigned)((blocks + PRE_BLOCK / 64 - 1) / (PRE_BLOCK / 64))), dim3(PRE_BLOCK), 0, st, par, n_reads, total, d_off, (const ulonglong2*)d_a,
+		                   d_sumq, sc.start_mask, sc.single_mask, sc.emit_mask, sc.block_cnt, sc.block_reads, d_gaps);
+	else
+		hipLaunchKernelGGL(k_prepass, dim3((unsigned)((blocks + PRE_BLOCK / 64 - 1) / (PRE_BLOCK / 64))), dim3(PRE_BLOCK), 0, st, par, n_reads, total, d_off, (const ulonglong2*)d_a,
+		                   d_sumq, sc.start_mask, sc.single_mask, sc.emit_mask, sc.block_cnt, sc.block_reads);
 	if ((e = launch_scan_u64(st, blocks, sc.block_cnt, sc.tile_tmp, d_counters)) != hipSuccess) return e;
 	hipLaunchKernelGGL(k_emit_units, dim3((unsigned)((words + 255) / 256 < 2048 ? (words + 255) / 256 : 2048)), dim3(256), 0, st, n_reads, words, d_off,
 	                   sc.start_mask, sc.single_mask, sc.block_cnt, sc.units_tmp, sc.hist, sc.block_reads);

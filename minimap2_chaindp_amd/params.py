@@ -37,6 +37,18 @@ def preset(name, **overrides):
     return ChainParams(**d)
 
 
+def read_gaps(max_gap, max_gap_ref, max_frag_len, is_sr, qlen_sum):
+    """The chaining gaps the reference derives per read from its total length (map.c:358-366; chaindp_read_gaps, needs no GPU):
+    (gap_ref int32[n], gap_qry int32[n]) for qlen_sum int32[n] -- what Device.set_read_gaps and the `gaps=` keyword take."""
+    import numpy as np
+    from . import chaindp
+    q = np.ascontiguousarray(qlen_sum, np.int32)
+    gr, gq = np.zeros(len(q), np.int32), np.zeros(len(q), np.int32)
+    chaindp.lib().chaindp_read_gaps(int(max_gap), int(max_gap_ref), int(max_frag_len), int(bool(is_sr)), len(q),
+                                    q.ctypes.data if len(q) else None, gr.ctypes.data if len(q) else None, gq.ctypes.data if len(q) else None)
+    return gr, gq
+
+
 # ---- chain_post / mm_set_mapq options (chaindp_post_opt_t) ---------------------------------------------------------------
 
 MM_F_NO_DIAG, MM_F_NO_DUAL, MM_F_CIGAR = 0x001, 0x002, 0x004          # minimap.h:8-10
