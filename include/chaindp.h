@@ -427,4 +427,6 @@ int chaindp_set_variant(chaindp_ctx_t *ctx, int force_general);
 #endif
 /* per-read chaining gaps (chaindp_read_gaps, chaindp_set_read_gaps): part of this ABI, declared in a header of their own */
 #include "chaindp_gaps.h"
+/* base-level alignment, the dual-gap extension DP (chaindp_ksw_extd): part of this ABI, declared in a header of its own */
+#include "chaindp_ksw.h"
 #endif

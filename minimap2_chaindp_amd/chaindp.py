@@ -24,6 +24,12 @@ SEED_DTYPE = np.dtype([("x", "<u8"), ("y", "<u8"), ("p", "<i4"), ("f", "<i4")]) 
 ABI_SYMBOLS = tuple(_cabi.prototypes("chaindp.h"))
 # ... and the ones of the header it includes for per-read gaps
 GAPS_SYMBOLS = tuple(_cabi.prototypes("chaindp_gaps.h"))
+# ... and for the alignment
+KSW_SYMBOLS = tuple(_cabi.prototypes("chaindp_ksw.h"))
+# KSW_EZ_* of the reference's ksw2.h that Device.ksw_extd takes, and the fields of its ez rows
+KSW_SCORE_ONLY, KSW_RIGHT, KSW_APPROX_MAX, KSW_EXTZ_ONLY, KSW_REV_CIGAR = 0x01, 0x02, 0x08, 0x40, 0x80
+KSW_EZ_FIELDS = ("max", "zdropped", "max_q", "max_t", "mqe", "mqe_t", "mte", "mte_q", "score", "reach_end")
+ERR_CAPACITY = -2
 
 # chaindp_reg_t == mm_reg1_t (minimap.h:100-115), 80 bytes; `bits` is the bit-field word (rev = bit 10)
 REG_DTYPE = np.dtype([(k, "<i4") for k in ("id", "cnt", "rid", "score", "qs", "qe", "rs", "re", "parent", "subsc", "as", "mlen", "blen", "n_sub", "score0")]
@@ -38,13 +44,13 @@ _lib = None
 
 
 def lib():
-    """The library, every function of include/chaindp.h, include/chaindp_gaps.h and include/chaindp_debug.h bound with the header's prototype."""
+    """The library, every function of include/chaindp.h, chaindp_gaps.h, chaindp_ksw.h and chaindp_debug.h bound with the header's prototype."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise ChainDPError(f"{LIB_PATH} is missing: build it with __graft_entry__.build() "
                                "(make -C minimap2_chaindp_amd/csrc); there is no fallback path")
-        _lib = _cabi.bind(C.CDLL(LIB_PATH), "chaindp.h", "chaindp_gaps.h", "chaindp_debug.h")
+        _lib = _cabi.bind(C.CDLL(LIB_PATH), "chaindp.h", "chaindp_gaps.h", "chaindp_ksw.h", "chaindp_debug.h")
     return _lib
 
 
@@ -60,6 +66,15 @@ def post_logf_patches():
 
 def device_count():
     return lib().chaindp_device_count()
+
+
+def ksw_routing():
+    """What Device.ksw_extd routes a problem by (needs no GPU): dict of lds_budget and the bytes of state per_target, per_query (both
+    lengths rounded up to 16 first) and fixed; a problem whose sum fits the budget keeps its state in LDS, others in global scratch;
+    a sum above wide_bytes gets wide_waves waves instead of one."""
+    out = (C.c_int64 * 6)()
+    lib().chaindp_ksw_debug_routing(out)
+    return dict(zip(("lds_budget", "per_target", "per_query", "fixed", "wide_bytes", "wide_waves"), (int(x) for x in out)))
 
 
 def _ptr(a):
@@ -505,6 +520,45 @@ class Device:
                                                    _ptr0(ref_len), len(ref_len), _ptr(soff), _ptr(regs), cap, _ptr(rep), C.byref(na))
         with self._gaps(gaps):
             return self._hits("map_frag_seqs", regs_cap, n_seqs, call, n_reads, n_bases=len(seq))
+
+    # -- base-level alignment: ksw_extd2_sse for a batch of problems (chaindp_ksw_extd)
+    def ksw_extd(self, bases, q_beg, q_len, t_beg, t_len, scoring, w, zdrop, end_bonus, flag, cigar_cap=None):
+        """Problem i aligns bases[q_beg[i] : q_beg[i] + q_len[i]] (query) to bases[t_beg[i] : t_beg[i] + t_len[i]] (target); bases uint8, codes
+        0..4.  scoring = (a, b, q, e, q2, e2) for the whole call; w, zdrop, end_bonus, flag per problem (a scalar serves all of them).
+        Returns (ez int32[n, 10] with the columns KSW_EZ_FIELDS, cigar_off int64[n + 1], cigar uint32[cigar_off[-1]]).  cigar_cap=None
+        makes room for sum(q_len + t_len) words, which no batch exceeds; with a cap that is too small the call raises ChainDPError and
+        err.ez / err.cigar_off hold what the C call filled in (cigar_off[-1] words are enough)."""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        q_beg, t_beg = np.ascontiguousarray(q_beg, np.int64), np.ascontiguousarray(t_beg, np.int64)
+        q_len, t_len = np.ascontiguousarray(q_len, np.int32), np.ascontiguousarray(t_len, np.int32)
+        n = len(q_beg)
+        if not (q_beg.shape == q_len.shape == t_beg.shape == t_len.shape == (n,)):
+            raise ValueError("q_beg, q_len, t_beg, t_len need one entry per problem each")
+        per = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.int32), (n,))) for v in (w, zdrop, end_bonus, flag)]
+        if n and (int((q_beg + q_len).max()) > len(bases) or int((t_beg + t_len).max()) > len(bases)):
+            raise ValueError("a problem reaches past the end of bases")
+        a, b, q, e, q2, e2 = (int(v) for v in scoring)
+        cap = int(q_len.astype(np.int64).sum() + t_len.astype(np.int64).sum()) if cigar_cap is None else int(cigar_cap)
+        ez, off, cigar = np.zeros((n, 10), np.int32), np.zeros(n + 1, np.int64), np.zeros(max(cap, 1), np.uint32)
+        rc = self._lib.chaindp_ksw_extd(self._ctx, n, _ptr0(bases), _ptr(q_beg), _ptr(q_len), _ptr(t_beg), _ptr(t_len), a, b, q, e, q2, e2,
+                                        *[_ptr(v) for v in per], _ptr(ez), _ptr(off), _ptr(cigar) if cap > 0 else None, max(cap, 0))
+        if rc == ERR_CAPACITY and int(off[-1]) > cap >= 0:
+            err = ChainDPError(f"chaindp error {rc}: {self._lib.chaindp_last_error(self._ctx).decode()}")
+            err.ez, err.cigar_off = ez, off
+            raise err
+        self._check(rc)
+        return ez, off, cigar[:int(off[-1])]
+
+    def ksw_route(self, n):
+        """The route each of the n problems of the last ksw_extd took, as the device reported it (test hook): 0 the reference's early
+        return, 1 state in LDS, 2 state in global scratch, 3 state in LDS and several waves."""
+        route = np.zeros(max(int(n), 1), np.int32)
+        self._check(self._lib.chaindp_ksw_debug_route(self._ctx, int(n), _ptr(route)))
+        return route[:int(n)]
+
+    def ksw_ms(self):
+        """Device milliseconds of the DP kernel in the last ksw_extd made while profiling was on (tuning hook); -1 before."""
+        return float(self._lib.chaindp_ksw_debug_ms(self._ctx))
 
     def set_frag_lds_cap(self, cap=64):
         """Test hook: fragments (and segments) with more than `cap` hits (0..64) keep their work arrays in global scratch, not LDS."""

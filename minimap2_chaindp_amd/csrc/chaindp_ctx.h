@@ -95,6 +95,11 @@ struct chaindp_ctx {
 	int n_logf = 0;
 	// reads of several segments: chaindp_frag_post (allocated on first use, grown with the batch)
 	chaindp::DevGrow frag_seq, frag_cnt, frag_u, frag_a, frag_stage, frag_z, frag_stacks, frag_out;
+	// alignment, chaindp_ksw_extd (allocated on first use, grown with the batch): sequences; problem records and their order; counter,
+	// CSR offsets and result words; the workgroups' slices of DP state (global route) and of path matrix; CIGARs as left and as packed
+	chaindp::DevGrow ksw_bases, ksw_prob, ksw_ez, ksw_state, ksw_path, ksw_cig, ksw_out;
+	double ksw_ms = -1;                        // k_ksw_extd's device time in the last call made while profiling was on
+	int64_t ksw_n = -1;                        // problems of the last chaindp_ksw_extd whose results are resident (chaindp_ksw_debug_route)
 	int frag_lds_cap = FRAG_LDS_CAP;           // chaindp_debug_set_frag_lds_cap (tests): fewer hits per fragment stay in LDS
 	// sketch (allocated on first use, grown with the batch)
 	chaindp::SketchArgs sk = {};

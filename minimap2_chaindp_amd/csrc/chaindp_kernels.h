@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "chaindp_ksw_plan.h"
 
 namespace chaindp {
 
@@ -340,6 +341,21 @@ hipError_t launch_scatter_seeds(hipStream_t st, int64_t n_reads, const int64_t *
 // rounds bytes up to 16: both buffers must have that much room
 hipError_t launch_copy_out(hipStream_t st, void *h_dst, const void *d_src, size_t bytes, int blocks);
 hipError_t launch_scatter_words(hipStream_t st, int64_t n_reads, const int64_t *d_woff, void *const *d_dst, const void *d_words);
+
+// the dual-gap extension alignment (ksw_extd2_sse, ksw2_extd2_sse.c): chaindp_ksw.hip.  One workgroup per problem; the device routes
+// every problem by its sizes: its nine byte arrays (the reference's one block, 8 T + Q + 16 bytes with T, Q = tlen, qlen rounded up
+// to 16) and H[] (4 T) stay in LDS while they fit KSW_LDS_BUDGET, else in the workgroup's slice of global scratch; a state above
+// KSW_WIDE_BYTES gets KSW_WIDE_WAVES waves.
+// (the routing constants, KswProb, KswScore and the sizes: chaindp_ksw_plan.h, host only code beside them)
+// n problems are taken from d_order (longest first) through *d_counter (zeroed here) by `grid` workgroups of `waves` waves (1 or
+// KSW_WIDE_WAVES); workgroup k keeps its global state in d_state + k * state_stride and its path matrix in d_path + k * path_stride.
+// lds_bytes: the largest state among the problems.  d_ez[][KSW_EZ_WORDS] and d_prob are indexed by problem; its CIGAR goes to d_cig + cig_beg.
+hipError_t launch_ksw_extd(hipStream_t st, int waves, int grid, size_t lds_bytes, int64_t n, const KswProb *d_prob, const int32_t *d_order,
+                           const uint8_t *d_bases, const KswScore &sc, uint8_t *d_state, size_t state_stride, uint8_t *d_path, size_t path_stride,
+                           int32_t *d_ez, uint32_t *d_cig, unsigned int *d_counter);
+// the CIGARs from where the problems left them to their CSR places: d_out[d_off[i] ..) = d_cig[d_prob[i].cig_beg .. + n_cigar)
+hipError_t launch_ksw_pack(hipStream_t st, int64_t n, const KswProb *d_prob, const int32_t *d_ez, const int64_t *d_off, const uint32_t *d_cig,
+                           uint32_t *d_out);
 
 } // namespace chaindp
 #endif
