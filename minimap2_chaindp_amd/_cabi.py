@@ -8,19 +8,20 @@ import functools
 import os
 import re
 
-from .params import ChainParams, PostOpt
+from .params import AlignOpt, ChainParams, PostOpt
 
 INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int, "unsigned int": C.c_uint, "uint32_t": C.c_uint, "int64_t": C.c_int64,
             "unsigned long": C.c_ulong, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
-_STRUCTS = {"const chaindp_params_t *": C.POINTER(ChainParams), "const chaindp_post_opt_t *": C.POINTER(PostOpt)}
+_STRUCTS = {"const chaindp_params_t *": C.POINTER(ChainParams), "const chaindp_post_opt_t *": C.POINTER(PostOpt),
+            "const chaindp_align_opt_t *": C.POINTER(AlignOpt)}
 _DECL = re.compile(r"(.+?[\s*])(\w+)\s*\(([^()]*)\)", re.S)      # ret name(args)
 
 
 def _ctype(decl, where, ret=False):
     """The ctypes type of one parameter (`const int32_t *qlen`, `size_t bytes[4]`) or, with ret, of a return type -- by type alone.
-    Every pointer but the two parameter structs' is an address (c_void_p): callers pass array addresses, also for `const char *seq`."""
+    Every pointer but the parameter structs' is an address (c_void_p): callers pass array addresses, also for `const char *seq`."""
     t = " ".join(decl.replace("*", " * ").split())
     if not ret:
         t, is_array = re.subn(r" ?\[ ?\w* ?\]$", "", t)

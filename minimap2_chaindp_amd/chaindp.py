@@ -29,6 +29,9 @@ KSW_SYMBOLS = tuple(_cabi.prototypes("chaindp_ksw.h"))
 # KSW_EZ_* of the reference's ksw2.h that Device.ksw_extd takes, and the fields of its ez rows
 KSW_SCORE_ONLY, KSW_RIGHT, KSW_APPROX_MAX, KSW_EXTZ_ONLY, KSW_REV_CIGAR = 0x01, 0x02, 0x08, 0x40, 0x80
 KSW_EZ_FIELDS = ("max", "zdropped", "max_q", "max_t", "mqe", "mqe_t", "mte", "mte_q", "score", "reach_end")
+# ... and for mm_align1
+ALIGN_SYMBOLS = tuple(_cabi.prototypes("chaindp_align.h"))
+ALIGN_EXTRA_DTYPE = np.dtype([(k, "<i4") for k in ("has_extra", "dp_score", "dp_max", "n_ambi", "n_cigar")])   # chaindp_align_extra_t
 ERR_CAPACITY = -2
 
 # chaindp_reg_t == mm_reg1_t (minimap.h:100-115), 80 bytes; `bits` is the bit-field word (rev = bit 10)
@@ -44,13 +47,14 @@ _lib = None
 
 
 def lib():
-    """The library, every function of include/chaindp.h, chaindp_gaps.h, chaindp_ksw.h and chaindp_debug.h bound with the header's prototype."""
+    """The library, every function of include/chaindp.h, chaindp_gaps.h, chaindp_ksw.h, chaindp_align.h and chaindp_debug.h bound with the
+    header's prototype."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise ChainDPError(f"{LIB_PATH} is missing: build it with __graft_entry__.build() "
                                "(make -C minimap2_chaindp_amd/csrc); there is no fallback path")
-        _lib = _cabi.bind(C.CDLL(LIB_PATH), "chaindp.h", "chaindp_gaps.h", "chaindp_ksw.h", "chaindp_debug.h")
+        _lib = _cabi.bind(C.CDLL(LIB_PATH), "chaindp.h", "chaindp_gaps.h", "chaindp_ksw.h", "chaindp_align.h", "chaindp_debug.h")
     return _lib
 
 
@@ -106,6 +110,8 @@ _CAPS = {
     "frag_post":     _Cap("total",   4,  True,  "raise", "again",      None),
     "map_frags":     _Cap("n_mini",  2,  True,  "raise", "frag_post",  "before"),
     "map_frag_seqs": _Cap("n_bases", 16, True,  "raise", "again",      "before"),  # again: the flip is part of the call
+    # align1: the room is for CIGAR words, not hits; a guess of one word per four read bases, the whole call again with the exact count
+    "align1":        _Cap("n_bases", 4,  True,  "raise", "again",      None),
 }
 
 
@@ -548,6 +554,56 @@ class Device:
             raise err
         self._check(rc)
         return ez, off, cigar[:int(off[-1])]
+
+    # -- base-level alignment of regions: mm_align1 around that DP (chaindp_align1)
+    def align_set_targets(self, seq_off, seq):
+        """The target sequences as characters (seq_off int64[n + 1], seq bytes / uint8), encoded on the device and kept resident until
+        the next call or align_clear_targets()."""
+        seq_off, seq = _arr(seq_off, np.int64), np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else _arr(seq, np.uint8)
+        if len(seq_off) < 1 or int(seq_off[-1]) != len(seq):
+            raise ValueError("seq_off must end at the number of bases")
+        self._check(self._lib.chaindp_align_set_targets(self._ctx, len(seq_off) - 1, _ptr(seq_off), _ptr0(seq)))
+
+    def align_clear_targets(self):
+        self._check(self._lib.chaindp_align_clear_targets(self._ctx))
+
+    def align1(self, opt, seq_off, seq, a_off, a, regs_off, regs, regs2=None, cigar_cap=None):
+        """mm_align1 for every region of every read (chaindp_align1): opt a params.AlignOpt; seq the reads' bases as characters; a uint64[n, 2]
+        each read's anchors after mm_squeeze_a; regs REG_DTYPE, `as` relative to the read's first anchor.  Nothing is changed in place.
+        Returns (a, regs, regs2, extra ALIGN_EXTRA_DTYPE[n_regions], cigar_off int64[n_regions + 1], cigar uint32[...]): the anchors with
+        their MM_SEED_IGNORE marks, the updated regions, what was split off (cnt 0 where nothing was; regs2 given: its other fields stay).
+        cigar_cap None: a guess, and the call again with the exact count where it was short (the _CAPS row); with a cap of the caller's
+        that is too small the call raises ChainDPError and err.a / .regs / .regs2 / .extra / .cigar_off hold what the C call filled in."""
+        seq_off, a_off, regs_off = _arr(seq_off, np.int64), _arr(a_off, np.int64), _arr(regs_off, np.int64)
+        seq = np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else _arr(seq, np.uint8)
+        a_in, regs_in = _arr(a, np.uint64).reshape(-1, 2), _arr(regs, REG_DTYPE)
+        n_reads, n_regs = len(seq_off) - 1, len(regs_in)
+        if len(a_off) != n_reads + 1 or len(regs_off) != n_reads + 1 or int(a_off[-1]) != len(a_in) or int(regs_off[-1]) != n_regs or int(seq_off[-1]) != len(seq):
+            raise ValueError("seq_off, a_off and regs_off need one entry per read and one more, and must end at the sizes of seq, a and regs")
+        row = _CAPS["align1"]
+        cap = int(cigar_cap) if cigar_cap is not None else max(len(seq) // row.divisor, REGS_CAP_FLOOR if row.floored else 1)
+        while True:
+            a_out, regs_out = a_in.copy(), regs_in.copy()
+            r2 = np.zeros(n_regs, REG_DTYPE) if regs2 is None else _arr(regs2, REG_DTYPE).copy()
+            extra, off, cigar = np.zeros(n_regs, ALIGN_EXTRA_DTYPE), np.zeros(n_regs + 1, np.int64), np.zeros(max(cap, 1), np.uint32)
+            rc = self._lib.chaindp_align1(self._ctx, C.byref(opt), n_reads, _ptr(seq_off), _ptr0(seq), _ptr(a_off), _ptr0(a_out), _ptr(regs_off),
+                                          _ptr0(regs_out), _ptr0(r2), _ptr0(extra), _ptr(off), _ptr(cigar) if cap > 0 else None, max(cap, 0))
+            short = rc == ERR_CAPACITY and int(off[-1]) > cap >= 0
+            if short and cigar_cap is None and row.retry == "again":
+                cap = int(off[-1])
+                continue
+            if short:
+                err = ChainDPError(f"chaindp error {rc}: {self._lib.chaindp_last_error(self._ctx).decode()}")
+                err.a, err.regs, err.regs2, err.extra, err.cigar_off = a_out, regs_out, r2, extra, off
+                raise err
+            self._check(rc)
+            return a_out, regs_out, r2, extra, off, cigar[:int(off[-1])]
+
+    def align_ms(self):
+        """Device milliseconds of the last align1 made while profiling was on (tuning hook): dict of plan, dp, zdrop, stitch, extra."""
+        ms = (C.c_double * 5)()
+        self._check(self._lib.chaindp_align_debug_ms(self._ctx, ms))
+        return dict(zip(("plan", "dp", "zdrop", "stitch", "extra"), (float(x) for x in ms)))
 
     def ksw_route(self, n):
         """The route each of the n problems of the last ksw_extd took, as the device reported it (test hook): 0 the reference's early

@@ -6,13 +6,52 @@
 using namespace chaindp;
 
 // a buffer of the stage: grown new-then-free; a device without room is the batch's problem (CHAINDP_ERR_CAPACITY), not the context's
-static int ksw_grow(chaindp_ctx *ctx, DevGrow &g, size_t need, const char *what)
+int chaindp::ksw_grow(chaindp_ctx *ctx, DevGrow &g, size_t need, const char *what, const char *who)
 {
 	const hipError_t e = dev_grow(ctx, g, need);
 	if (e == hipSuccess) return CHAINDP_OK;
 	(void)hipGetLastError();
-	ctx->err = std::string("chaindp_ksw_extd: ") + what + " (" + std::to_string((unsigned long long)need) + " bytes): " + hipGetErrorString(e);
+	ctx->err = std::string(who) + ": " + what + " (" + std::to_string((unsigned long long)need) + " bytes): " + hipGetErrorString(e);
 	return e == hipErrorOutOfMemory ? CHAINDP_ERR_CAPACITY : CHAINDP_ERR_HIP;
+}
+
+// every buffer a planned batch needs (the stream is idle: a buffer that grows is freed)
+int chaindp::ksw_reserve(chaindp_ctx *ctx, const KswPlan &pl, int64_t n_bases, const char *who)
+{
+	const size_t N = pl.prob.size();
+	int rc;
+	if ((rc = ksw_grow(ctx, ctx->ksw_bases, (size_t)n_bases + 16, "sequences", who))) return rc;
+	if ((rc = ksw_grow(ctx, ctx->ksw_prob, N * sizeof(KswProb) + N * sizeof(int32_t) + 16, "problem records", who))) return rc;
+	if ((rc = ksw_grow(ctx, ctx->ksw_ez, N * KSW_EZ_WORDS * sizeof(int32_t) + (N + 1) * sizeof(int64_t) + 32, "results", who))) return rc;
+	if ((rc = ksw_grow(ctx, ctx->ksw_state, (size_t)pl.grid[0] * pl.state_stride + 16, "DP state", who))) return rc;
+	if ((rc = ksw_grow(ctx, ctx->ksw_path, (size_t)pl.grid[0] * pl.path_stride[0] + (size_t)pl.grid[1] * pl.path_stride[1] + 16, "path matrices", who))) return rc;
+	if ((rc = ksw_grow(ctx, ctx->ksw_cig, (size_t)pl.cig_words * sizeof(uint32_t) + 16, "CIGAR staging", who))) return rc;
+	ctx->ksw_n = 0;
+	return CHAINDP_OK;
+}
+
+// the records and their order up, the two launches; the bases are on the device already.  ev0 / ev1 (or null): recorded around the launches
+int chaindp::ksw_dispatch(chaindp_ctx *ctx, const KswPlan &pl, hipEvent_t ev0, hipEvent_t ev1)
+{
+	const size_t N = pl.prob.size();
+	hipStream_t st = ctx->stream;
+	// ksw_prob: the records, then the order; ksw_ez: the two launches' counters (8 bytes each), the CSR offsets, the result words
+	KswProb *d_prob = (KswProb*)ctx->ksw_prob.p;
+	int32_t *d_order = (int32_t*)(d_prob + N);
+	unsigned int *d_counter = (unsigned int*)ctx->ksw_ez.p;
+	int32_t *d_ez = (int32_t*)((int64_t*)ctx->ksw_ez.p + 2 + N + 1);
+	HIP_TRY(ctx, hipMemcpyAsync(d_prob, pl.prob.data(), N * sizeof(KswProb), hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, hipMemcpyAsync(d_order, pl.order.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, st));
+	if (ev0) HIP_TRY(ctx, hipEventRecord(ev0, st));
+	// the wide problems first: theirs are the long workgroups, the one-wave ones fill in behind them
+	HIP_TRY(ctx, launch_ksw_extd(st, KSW_WIDE_WAVES, pl.grid[1], pl.lds_bytes[1], pl.count[1], d_prob, d_order + pl.count[0], (const uint8_t*)ctx->ksw_bases.p,
+	                             pl.sc, nullptr, 0, (uint8_t*)ctx->ksw_path.p + (size_t)pl.grid[0] * pl.path_stride[0], pl.path_stride[1], d_ez,
+	                             (uint32_t*)ctx->ksw_cig.p, d_counter + 2));
+	HIP_TRY(ctx, launch_ksw_extd(st, 1, pl.grid[0], pl.lds_bytes[0], pl.count[0], d_prob, d_order, (const uint8_t*)ctx->ksw_bases.p, pl.sc,
+	                             (uint8_t*)ctx->ksw_state.p, pl.state_stride, (uint8_t*)ctx->ksw_path.p, pl.path_stride[0], d_ez, (uint32_t*)ctx->ksw_cig.p,
+	                             d_counter));
+	if (ev1) HIP_TRY(ctx, hipEventRecord(ev1, st));
+	return CHAINDP_OK;
 }
 
 extern "C" int chaindp_ksw_extd(chaindp_ctx_t *ctx, int64_t n, const uint8_t *bases, const int64_t *q_beg, const int32_t *q_len,
@@ -34,23 +73,12 @@ extern "C" int chaindp_ksw_extd(chaindp_ctx_t *ctx, int64_t n, const uint8_t *ba
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // a buffer that grows is freed: nothing of an earlier call may be in flight
 	const size_t N = (size_t)n;
 	int rc;
-	if ((rc = ksw_grow(ctx, ctx->ksw_bases, (size_t)pl.n_bases + 16, "sequences"))) return rc;
-	if ((rc = ksw_grow(ctx, ctx->ksw_prob, N * sizeof(KswProb) + N * sizeof(int32_t) + 16, "problem records"))) return rc;
-	if ((rc = ksw_grow(ctx, ctx->ksw_ez, N * KSW_EZ_WORDS * sizeof(int32_t) + (N + 1) * sizeof(int64_t) + 32, "results"))) return rc;
-	if ((rc = ksw_grow(ctx, ctx->ksw_state, (size_t)pl.grid[0] * pl.state_stride + 16, "DP state"))) return rc;
-	if ((rc = ksw_grow(ctx, ctx->ksw_path, (size_t)pl.grid[0] * pl.path_stride[0] + (size_t)pl.grid[1] * pl.path_stride[1] + 16, "path matrices"))) return rc;
-	if ((rc = ksw_grow(ctx, ctx->ksw_cig, (size_t)pl.cig_words * sizeof(uint32_t) + 16, "CIGAR staging"))) return rc;
-	ctx->ksw_n = 0;
+	if ((rc = ksw_reserve(ctx, pl, pl.n_bases, "chaindp_ksw_extd"))) return rc;
 	hipStream_t st = ctx->stream;
-	// ksw_prob: the records, then the order; ksw_ez: the two launches' counters (8 bytes each), the CSR offsets, the result words
 	KswProb *d_prob = (KswProb*)ctx->ksw_prob.p;
-	int32_t *d_order = (int32_t*)(d_prob + N);
-	unsigned int *d_counter = (unsigned int*)ctx->ksw_ez.p;
 	int64_t *d_off = (int64_t*)ctx->ksw_ez.p + 2;
 	int32_t *d_ez = (int32_t*)(d_off + N + 1);
 	if (pl.n_bases) HIP_TRY(ctx, hipMemcpyAsync(ctx->ksw_bases.p, bases, (size_t)pl.n_bases, hipMemcpyHostToDevice, st));
-	HIP_TRY(ctx, hipMemcpyAsync(d_prob, pl.prob.data(), N * sizeof(KswProb), hipMemcpyHostToDevice, st));
-	HIP_TRY(ctx, hipMemcpyAsync(d_order, pl.order.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, st));
 	struct Events {                                       // while profiling is on: the DP kernels' own time, apart from the copies around them
 		hipEvent_t e[2] = {nullptr, nullptr};
 		~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
@@ -59,16 +87,8 @@ extern "C" int chaindp_ksw_extd(chaindp_ctx_t *ctx, int64_t n, const uint8_t *ba
 	if (ctx->prof) {
 		HIP_TRY(ctx, hipEventCreate(&ev.e[0]));
 		HIP_TRY(ctx, hipEventCreate(&ev.e[1]));
-		HIP_TRY(ctx, hipEventRecord(ev[0], st));
 	}
-	// the wide problems first: theirs are the long workgroups, the one-wave ones fill in behind them
-	HIP_TRY(ctx, launch_ksw_extd(st, KSW_WIDE_WAVES, pl.grid[1], pl.lds_bytes[1], pl.count[1], d_prob, d_order + pl.count[0], (const uint8_t*)ctx->ksw_bases.p,
-	                             pl.sc, nullptr, 0, (uint8_t*)ctx->ksw_path.p + (size_t)pl.grid[0] * pl.path_stride[0], pl.path_stride[1], d_ez,
-	                             (uint32_t*)ctx->ksw_cig.p, d_counter + 2));
-	HIP_TRY(ctx, launch_ksw_extd(st, 1, pl.grid[0], pl.lds_bytes[0], pl.count[0], d_prob, d_order, (const uint8_t*)ctx->ksw_bases.p, pl.sc,
-	                             (uint8_t*)ctx->ksw_state.p, pl.state_stride, (uint8_t*)ctx->ksw_path.p, pl.path_stride[0], d_ez, (uint32_t*)ctx->ksw_cig.p,
-	                             d_counter));
-	if (ev[0]) HIP_TRY(ctx, hipEventRecord(ev[1], st));
+	if ((rc = ksw_dispatch(ctx, pl, ev[0], ev[1]))) return rc;
 	std::vector<int32_t> ez(N * KSW_EZ_WORDS);
 	HIP_TRY(ctx, hipMemcpyAsync(ez.data(), d_ez, ez.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -88,7 +108,7 @@ extern "C" int chaindp_ksw_extd(chaindp_ctx_t *ctx, int64_t n, const uint8_t *ba
 		return CHAINDP_ERR_CAPACITY;
 	}
 	if (total == 0) return CHAINDP_OK;
-	if ((rc = ksw_grow(ctx, ctx->ksw_out, (size_t)total * sizeof(uint32_t), "CIGARs"))) return rc;
+	if ((rc = ksw_grow(ctx, ctx->ksw_out, (size_t)total * sizeof(uint32_t), "CIGARs", "chaindp_ksw_extd"))) return rc;
 	HIP_TRY(ctx, hipMemcpyAsync(d_off, cigar_off, (N + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
 	HIP_TRY(ctx, launch_ksw_pack(st, n, d_prob, d_ez, d_off, (const uint32_t*)ctx->ksw_cig.p, (uint32_t*)ctx->ksw_out.p));
 	HIP_TRY(ctx, hipMemcpyAsync(cigar, ctx->ksw_out.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));

@@ -100,6 +100,12 @@ struct chaindp_ctx {
 	chaindp::DevGrow ksw_bases, ksw_prob, ksw_ez, ksw_state, ksw_path, ksw_cig, ksw_out;
 	double ksw_ms = -1;                        // k_ksw_extd's device time in the last call made while profiling was on
 	int64_t ksw_n = -1;                        // problems of the last chaindp_ksw_extd whose results are resident (chaindp_ksw_debug_route)
+	// mm_align1, chaindp_align1 (allocated on first use, grown with the batch): the targets' codes and offsets; the reads, anchors and
+	// regions of the batch with their offsets; the regions' plans, problem slots and side records; the first pass's results and CIGARs
+	// kept over the second pass; the Z-drop codes and the second pass's index; the stitched CIGARs, the results, the packed CIGARs
+	chaindp::DevGrow al_tgt, al_toff, al_in, al_reg, al_slot, al_side, al_ez1, al_cig1, al_code, al_stage, al_res, al_out;
+	std::vector<int64_t> al_t_off;             // the resident targets' offsets (host copy); empty: none set
+	double al_ms[5] = {-1, -1, -1, -1, -1};    // plan, DP, zdrop, stitch, extra of the last chaindp_align1 made while profiling was on
 	int frag_lds_cap = FRAG_LDS_CAP;           // chaindp_debug_set_frag_lds_cap (tests): fewer hits per fragment stay in LDS
 	// sketch (allocated on first use, grown with the batch)
 	chaindp::SketchArgs sk = {};
@@ -175,6 +181,11 @@ PostOpt to_post_opt(const chaindp_post_opt_t *o);
 int post_require_hits(chaindp_ctx *ctx, const char *who);
 int post_stage_rep_len(chaindp_ctx *ctx, const int32_t *rep_len, int64_t R, const int32_t **d_rep);
 int post_finish(chaindp_ctx *ctx);
+
+// chaindp_abi_ksw.cpp: the parts of chaindp_ksw_extd that chaindp_align1 runs on records its own kernels made
+int ksw_grow(chaindp_ctx *ctx, DevGrow &g, size_t need, const char *what, const char *who);
+int ksw_reserve(chaindp_ctx *ctx, const KswPlan &pl, int64_t n_bases, const char *who);
+int ksw_dispatch(chaindp_ctx *ctx, const KswPlan &pl, hipEvent_t ev0, hipEvent_t ev1);
 
 // ---- stage entry points that other stages call
 int collect_seeds_impl(chaindp_ctx *ctx, const chaindp_index_t *ix, int flag, int max_occ, int64_t n_reads,

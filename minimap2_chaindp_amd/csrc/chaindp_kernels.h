@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "chaindp_ksw_plan.h"
+#include "chaindp_align_plan.h"
 
 namespace chaindp {
 
@@ -356,6 +357,28 @@ hipError_t launch_ksw_extd(hipStream_t st, int waves, int grid, size_t lds_bytes
 // the CIGARs from where the problems left them to their CSR places: d_out[d_off[i] ..) = d_cig[d_prob[i].cig_beg .. + n_cigar)
 hipError_t launch_ksw_pack(hipStream_t st, int64_t n, const KswProb *d_prob, const int32_t *d_ez, const int64_t *d_off, const uint32_t *d_cig,
                            uint32_t *d_out);
+
+// mm_align1 around that DP (align.c:423-636): align/chaindp_align.hip.  One wave per region or per problem; the records and the host's part
+// between the kernels: chaindp_align_plan.h.  Everything below is device memory.
+struct AlignDev {
+	int n_regs; int64_t n_prob;                     // regions; problems of the first pass (the compact list)
+	const int32_t *reg_read; const int64_t *seq_off; const char *seq; const int64_t *a_off; void *a; int32_t *regs, *regs2;
+	const int64_t *t_off; const uint8_t *tcodes;    // the resident targets
+	const int64_t *slot_off; KswProb *slots; AlignSide *side; AlignReg *areg; int32_t *kbuf;     // k_align_plan's output, per slot and per region
+	const KswProb *prob; const int32_t *src_slot; const int64_t *first;                         // the compact list: records, slots, a region's first problem
+	const int32_t *ez1; const uint32_t *cig1;       // the first pass's results and CIGARs
+	int32_t *code; const int32_t *sec;              // mm_test_zdrop's code per problem; its index in the second pass or -1
+	uint32_t *stage; AlignStitch *stitch; int32_t *extra;
+};
+hipError_t launch_align_encode(hipStream_t st, int64_t n, const char *d_seq, uint8_t *d_codes);
+hipError_t launch_align_plan(hipStream_t st, const AlignOpt &o, const AlignDev &d);
+hipError_t launch_align_gather(hipStream_t st, const AlignDev &d, uint8_t *d_bases);
+// lds_t: entries per LDS array of the inversion score, the longest target stretch it can meet + 1
+hipError_t launch_align_zdrop(hipStream_t st, const AlignOpt &o, const AlignDev &d, const uint8_t *d_bases, const int32_t *d_ez, const uint32_t *d_cig, int lds_t);
+hipError_t launch_align_stitch(hipStream_t st, const AlignOpt &o, const AlignDev &d, int64_t cig_total, const KswProb *d_prob2, const int32_t *d_ez2,
+                               const uint32_t *d_cig2);
+hipError_t launch_align_extra(hipStream_t st, const AlignOpt &o, const AlignDev &d);
+hipError_t launch_align_pack(hipStream_t st, const AlignDev &d, const int64_t *d_off, uint32_t *d_out);
 
 } // namespace chaindp
 #endif

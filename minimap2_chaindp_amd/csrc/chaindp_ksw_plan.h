@@ -68,33 +68,18 @@ struct KswPlan {
 };
 #define KSW_PATH_TOTAL ((size_t)1 << 32)    // the path slices of a launch's workgroups together stay below this while there are 64 or more
 
-// 0 and a filled plan, or -1 (CHAINDP_ERR_ARG) with plan.err.  cus: compute units of the device.
-inline int ksw_plan(int64_t n, const uint8_t *bases, const int64_t *q_beg, const int32_t *q_len, const int64_t *t_beg, const int32_t *t_len,
-                    int a, int b, int q, int e, int q2, int e2, const int32_t *w, const int32_t *zdrop, const int32_t *end_bonus,
-                    const int32_t *flag, int cus, KswPlan &pl)
+// From the records in pl.prob (lengths, band, flag; pl.sc set): cig_beg of every problem, the order, the two launches' sizes.
+// cus: compute units of the device.  What chaindp_align1 calls on the records its planning kernel made.
+inline void ksw_plan_route(KswPlan &pl, int cus)
 {
-	pl = KswPlan();
-	if (n < 0) { pl.err = "chaindp_ksw_extd: negative problem count"; return -1; }
-	if (n > 0x7fffffff) { pl.err = "chaindp_ksw_extd: more than 2^31 - 1 problems"; return -1; }
-	for (int v : {a, b, q, e, q2, e2})
-		if (v < 0 || v > 127) { pl.err = "chaindp_ksw_extd: a, b, q, e, q2, e2 must lie in 0..127"; return -1; }
-	if (n > 0 && (!q_beg || !q_len || !t_beg || !t_len || !w || !zdrop || !end_bonus || !flag)) { pl.err = "chaindp_ksw_extd: NULL per-problem array"; return -1; }
-	const int qe0 = q + e;
-	if (q2 + e2 < q + e) { std::swap(q, q2); std::swap(e, e2); }        // ksw2_extd2_sse.c:70
-	pl.sc = KswScore{a, b, q, e, q2, e2, qe0, b > 2 * (q + e)};
-	pl.prob.resize((size_t)n);
+	const int64_t n = (int64_t)pl.prob.size();
 	std::vector<int64_t> work((size_t)n);
+	pl.cig_words = 0;
+	for (int c = 0; c < 2; ++c) { pl.count[c] = 0; pl.lds_bytes[c] = 0; pl.path_stride[c] = 0; }
+	pl.state_stride = 0;
 	for (int64_t i = 0; i < n; ++i) {
-		if (flag[i] & ~0xcb) { pl.err = "chaindp_ksw_extd: flag bit outside SCORE_ONLY, RIGHT, APPROX_MAX, EXTZ_ONLY, REV_CIGAR in problem " + std::to_string(i); return -1; }
-		if (q_len[i] < 0 || t_len[i] < 0 || q_beg[i] < 0 || t_beg[i] < 0) { pl.err = "chaindp_ksw_extd: negative start or length in problem " + std::to_string(i); return -1; }
-		if ((int64_t)q_len[i] + t_len[i] >= KSW_MAX_SPAN) { pl.err = "chaindp_ksw_extd: q_len + t_len of 2^27 or more in problem " + std::to_string(i); return -1; }
-		if (q_beg[i] > INT64_MAX - q_len[i] || t_beg[i] > INT64_MAX - t_len[i]) { pl.err = "chaindp_ksw_extd: range past int64 in problem " + std::to_string(i); return -1; }
-		if ((q_len[i] > 0 || t_len[i] > 0) && !bases) { pl.err = "chaindp_ksw_extd: NULL bases"; return -1; }
 		KswProb &p = pl.prob[(size_t)i];
-		const int32_t wmax = std::max(q_len[i], t_len[i]);
-		p = KswProb{q_beg[i], t_beg[i], pl.cig_words, q_len[i], t_len[i], std::min(w[i], wmax), zdrop[i], end_bonus[i], flag[i]};
-		if (q_len[i] > 0) pl.n_bases = std::max(pl.n_bases, q_beg[i] + q_len[i]);
-		if (t_len[i] > 0) pl.n_bases = std::max(pl.n_bases, t_beg[i] + t_len[i]);
+		p.cig_beg = pl.cig_words;
 		const int route = ksw_route(p.qlen, p.tlen, pl.sc.skip);
 		work[(size_t)i] = 0;
 		if (route == KSW_ROUTE_NONE) continue;
@@ -107,11 +92,6 @@ inline int ksw_plan(int64_t n, const uint8_t *bases, const int64_t *q_beg, const
 		const size_t state = (size_t)ksw_state_bytes(p.qlen, p.tlen);
 		if (route == KSW_ROUTE_GLOBAL) pl.state_stride = std::max(pl.state_stride, state);
 		else pl.lds_bytes[route == KSW_ROUTE_WIDE] = std::max(pl.lds_bytes[route == KSW_ROUTE_WIDE], state);
-	}
-	for (int64_t i = 0; i < n; ++i) {
-		const KswProb &p = pl.prob[(size_t)i];
-		for (int64_t k = 0; k < p.qlen; ++k) if (bases[p.q_beg + k] > 4) { pl.err = "chaindp_ksw_extd: base above 4 in the query of problem " + std::to_string(i); return -1; }
-		for (int64_t k = 0; k < p.tlen; ++k) if (bases[p.t_beg + k] > 4) { pl.err = "chaindp_ksw_extd: base above 4 in the target of problem " + std::to_string(i); return -1; }
 	}
 	pl.state_stride = (pl.state_stride + 255) / 256 * 256;
 	for (int c = 0; c < 2; ++c) pl.path_stride[c] = (pl.path_stride[c] + 255) / 256 * 256;
@@ -132,6 +112,48 @@ inline int ksw_plan(int64_t n, const uint8_t *bases, const int64_t *q_beg, const
 	// ... fewer while the launch's path slices together would pass KSW_PATH_TOTAL
 	for (int c = 0; c < 2; ++c)
 		while (pl.grid[c] > 64 && (size_t)pl.grid[c] * pl.path_stride[c] > KSW_PATH_TOTAL) pl.grid[c] = (pl.grid[c] + 1) / 2;
+}
+
+// the scoring set as the kernel takes it; false where a value lies outside 0..127
+inline bool ksw_plan_score(int a, int b, int q, int e, int q2, int e2, KswScore &sc)
+{
+	for (int v : {a, b, q, e, q2, e2})
+		if (v < 0 || v > 127) return false;
+	const int qe0 = q + e;
+	if (q2 + e2 < q + e) { std::swap(q, q2); std::swap(e, e2); }        // ksw2_extd2_sse.c:70
+	sc = KswScore{a, b, q, e, q2, e2, qe0, b > 2 * (q + e)};
+	return true;
+}
+
+// 0 and a filled plan, or -1 (CHAINDP_ERR_ARG) with plan.err.  cus: compute units of the device.
+inline int ksw_plan(int64_t n, const uint8_t *bases, const int64_t *q_beg, const int32_t *q_len, const int64_t *t_beg, const int32_t *t_len,
+                    int a, int b, int q, int e, int q2, int e2, const int32_t *w, const int32_t *zdrop, const int32_t *end_bonus,
+                    const int32_t *flag, int cus, KswPlan &pl)
+{
+	pl = KswPlan();
+	if (n < 0) { pl.err = "chaindp_ksw_extd: negative problem count"; return -1; }
+	if (n > 0x7fffffff) { pl.err = "chaindp_ksw_extd: more than 2^31 - 1 problems"; return -1; }
+	if (!ksw_plan_score(a, b, q, e, q2, e2, pl.sc)) { pl.err = "chaindp_ksw_extd: a, b, q, e, q2, e2 must lie in 0..127"; return -1; }
+	if (n > 0 && (!q_beg || !q_len || !t_beg || !t_len || !w || !zdrop || !end_bonus || !flag)) { pl.err = "chaindp_ksw_extd: NULL per-problem array"; return -1; }
+	pl.prob.resize((size_t)n);
+	for (int64_t i = 0; i < n; ++i) {
+		if (flag[i] & ~0xcb) { pl.err = "chaindp_ksw_extd: flag bit outside SCORE_ONLY, RIGHT, APPROX_MAX, EXTZ_ONLY, REV_CIGAR in problem " + std::to_string(i); return -1; }
+		if (q_len[i] < 0 || t_len[i] < 0 || q_beg[i] < 0 || t_beg[i] < 0) { pl.err = "chaindp_ksw_extd: negative start or length in problem " + std::to_string(i); return -1; }
+		if ((int64_t)q_len[i] + t_len[i] >= KSW_MAX_SPAN) { pl.err = "chaindp_ksw_extd: q_len + t_len of 2^27 or more in problem " + std::to_string(i); return -1; }
+		if (q_beg[i] > INT64_MAX - q_len[i] || t_beg[i] > INT64_MAX - t_len[i]) { pl.err = "chaindp_ksw_extd: range past int64 in problem " + std::to_string(i); return -1; }
+		if ((q_len[i] > 0 || t_len[i] > 0) && !bases) { pl.err = "chaindp_ksw_extd: NULL bases"; return -1; }
+		KswProb &p = pl.prob[(size_t)i];
+		const int32_t wmax = std::max(q_len[i], t_len[i]);
+		p = KswProb{q_beg[i], t_beg[i], 0, q_len[i], t_len[i], std::min(w[i], wmax), zdrop[i], end_bonus[i], flag[i]};
+		if (q_len[i] > 0) pl.n_bases = std::max(pl.n_bases, q_beg[i] + q_len[i]);
+		if (t_len[i] > 0) pl.n_bases = std::max(pl.n_bases, t_beg[i] + t_len[i]);
+	}
+	for (int64_t i = 0; i < n; ++i) {
+		const KswProb &p = pl.prob[(size_t)i];
+		for (int64_t k = 0; k < p.qlen; ++k) if (bases[p.q_beg + k] > 4) { pl.err = "chaindp_ksw_extd: base above 4 in the query of problem " + std::to_string(i); return -1; }
+		for (int64_t k = 0; k < p.tlen; ++k) if (bases[p.t_beg + k] > 4) { pl.err = "chaindp_ksw_extd: base above 4 in the target of problem " + std::to_string(i); return -1; }
+	}
+	ksw_plan_route(pl, cus);
 	return 0;
 }
 

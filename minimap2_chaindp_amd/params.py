@@ -88,3 +88,37 @@ def post_preset(name, **overrides):
     d.update(POST_PRESETS[name])
     d.update(overrides)
     return PostOpt(**d)
+
+
+# ---- mm_align1 options (chaindp_align_opt_t) ------------------------------------------------------------------------------
+
+class AlignOpt(C.Structure):
+    """Mirror of chaindp_align_opt_t (include/chaindp_align.h): the fields of mm_mapopt_t and mm_idx_t that mm_align1 reads."""
+    _fields_ = [(k, C.c_int32) for k in ("a", "b", "q", "e", "q2", "e2", "bw", "zdrop", "zdrop_inv", "end_bonus", "min_cnt", "min_chain_score",
+                                         "min_dp_max", "min_ksw_len", "max_gap", "flag", "k", "is_hpc")]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# options.c:29-48 (mm_mapopt_init) and, per preset, what mm_set_opt changes of it (options.c:84-114); flag holds only the bits
+# mm_align1 looks at (none of these presets sets one)
+_ALIGN_DEFAULTS = dict(a=2, b=4, q=4, e=2, q2=24, e2=1, bw=500, zdrop=400, zdrop_inv=200, end_bonus=-1, min_cnt=3, min_chain_score=40,
+                       min_dp_max=80, min_ksw_len=200, max_gap=5000, flag=0, k=15, is_hpc=0)
+ALIGN_PRESETS = {
+    "map-ont": {},
+    "map-pb": dict(k=19, is_hpc=1),
+    "ava-ont": dict(min_chain_score=100, max_gap=10000),
+    "ava-pb": dict(k=19, is_hpc=1, min_chain_score=100, max_gap=10000, bw=2000),
+    "asm5": dict(k=19, a=1, b=19, q=39, q2=81, e=3, e2=1, zdrop=200, zdrop_inv=200, min_dp_max=200),
+    "asm10": dict(k=19, a=1, b=9, q=16, q2=41, e=2, e2=1, zdrop=200, zdrop_inv=200, min_dp_max=200),
+    "asm20": dict(k=19, a=1, b=4, q=6, q2=26, e=2, e2=1, zdrop=200, zdrop_inv=200, min_dp_max=200),
+}
+
+
+def align_opt(name, **overrides):
+    """chaindp_align_opt_t of a long-read preset, what Device.align1 takes."""
+    d = dict(_ALIGN_DEFAULTS)
+    d.update(ALIGN_PRESETS[name])
+    d.update(overrides)
+    return AlignOpt(**d)

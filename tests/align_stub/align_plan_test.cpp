@@ -1,0 +1,129 @@
+// The host planning of chaindp_align1 on its own: every refusal, the empty calls, and seeded batches whose slots, compact problem list
+// and DP plan are checked for what the kernels index.  The arrays are heap blocks of exactly the stated lengths, so that a read past
+// an end is a sanitizer report.
+#include <assert.h>
+#include <stdio.h>
+#include <memory>
+#include <random>
+#include "../../minimap2_chaindp_amd/csrc/chaindp_align_plan.h"
+
+using namespace chaindp;
+
+template <typename T> static std::unique_ptr<T[]> exact(const std::vector<T> &v)
+{
+	std::unique_ptr<T[]> p(new T[v.size() ? v.size() : 1]);
+	for (size_t i = 0; i < v.size(); ++i) p[i] = v[i];
+	return p;
+}
+
+struct Batch {
+	AlignOpt o{2, 4, 4, 2, 24, 1, 500, 400, 200, -1, 3, 40, 80, 200, 5000, 0, 15, 0};
+	std::vector<int64_t> seq_off{0}, a_off{0}, regs_off{0}, t_off{0};
+	std::vector<uint64_t> a;          // x, y pairs
+	std::vector<int32_t> regs;        // AL_REG_WORDS per region
+	void target(int len) { t_off.push_back(t_off.back() + len); }
+	void read(int qlen) { seq_off.push_back(seq_off.back() + qlen); a_off.push_back((int64_t)a.size() / 2); regs_off.push_back((int64_t)regs.size() / AL_REG_WORDS); }
+	void anchor(int rev, int rid, uint32_t x, uint32_t y, int span = 15) { a.push_back((uint64_t)rev << 63 | (uint64_t)rid << 32 | x); a.push_back((uint64_t)span << 32 | y); a_off.back() = (int64_t)a.size() / 2; }
+	void region(int as, int cnt) { std::vector<int32_t> r(AL_REG_WORDS, 0); r[1] = cnt; r[10] = as; regs.insert(regs.end(), r.begin(), r.end()); regs_off.back() = (int64_t)regs.size() / AL_REG_WORDS; }
+	int plan(AlignPlan &pl) const
+	{
+		auto so = exact(seq_off), ao = exact(a_off), ro = exact(regs_off), to = exact(t_off);
+		auto av = exact(a);
+		auto rv = exact(regs);
+		return align_plan(&o, (int64_t)seq_off.size() - 1, so.get(), ao.get(), a.empty() ? nullptr : av.get(), ro.get(), regs.empty() ? nullptr : rv.get(),
+		                  (int64_t)t_off.size() - 1, to.get(), pl);
+	}
+};
+
+static Batch simple()
+{
+	Batch b;
+	b.target(1000); b.target(500);
+	b.read(300);
+	for (int i = 0; i < 6; ++i) b.anchor(0, 0, 100 + 40 * i, 20 + 40 * i);
+	b.region(0, 3); b.region(3, 3);
+	b.read(200);
+	for (int i = 0; i < 4; ++i) b.anchor(1, 1, 50 + 30 * i, 30 + 30 * i);
+	b.region(0, 4); b.region(0, 0);
+	return b;
+}
+
+int main()
+{
+	AlignPlan pl;
+	int refused = 0, planned = 0;
+	{ Batch b; assert(b.plan(pl) == 0 && pl.n_regs == 0 && pl.n_slots == 0 && pl.slot_off.size() == 1); }            // no reads
+	{ Batch b; b.target(10); b.read(50); b.read(0); assert(b.plan(pl) == 0 && pl.n_regs == 0 && pl.n_slots == 0); } // reads without regions
+	Batch base = simple();
+	assert(base.plan(pl) == 0 && pl.n_regs == 4 && pl.n_slots == 4 + 4 + 5 + 0 && pl.reg_read[2] == 1 && pl.slot_off[3] == pl.slot_off[4]);
+	auto refuse = [&](Batch b) { assert(b.plan(pl) == -1 && !pl.err.empty()); ++refused; };
+	{ Batch b = base; b.o.flag = AL_F_SR; refuse(b); }
+	{ Batch b = base; b.o.flag = AL_F_SPLICE | 0x4; refuse(b); }
+	{ Batch b = base; b.o.q2 = b.o.q; b.o.e2 = b.o.e; refuse(b); }
+	{ Batch b = base; b.o.a = 128; refuse(b); }
+	{ Batch b = base; b.o.e2 = -1; refuse(b); }
+	{ Batch b = base; b.o.max_gap = AL_MAX_GAP + 1; refuse(b); }
+	{ Batch b = base; b.a[2 * 1] ^= 1ull << 63; refuse(b); }                       // another strand inside a region
+	{ Batch b = base; b.a[2 * 4] += 1ull << 32; refuse(b); }                       // another rid inside a region
+	{ Batch b = base; b.a[2 * 7] += 5ull << 32; refuse(b); }                       // a rid that is no target (the whole region carries it: read 1's first)
+	{ Batch b = base; for (int i = 6; i < 10; ++i) b.a[2 * i] += 1ull << 32; refuse(b); }   // ... all four anchors: no such target
+	{ Batch b = base; b.a[2 * 5] = (b.a[2 * 5] & ~0xffffffffull) | 1000; refuse(b); }   // x at the target's length
+	{ Batch b = base; b.a[2 * 2 + 1] = (b.a[2 * 2 + 1] & ~0xffffffffull) | 300; refuse(b); }   // y at the read's length
+	{ Batch b = base; b.regs[1] = 7; refuse(b); }                                  // a region past its read's anchors
+	{ Batch b = base; b.regs[10] = -1; refuse(b); }
+	{ Batch b = base; b.regs[AL_REG_WORDS * 2 + 1] = -2; refuse(b); }
+	{ Batch b = base; b.seq_off[1] = 500; b.seq_off[2] = 400; refuse(b); }
+	{ Batch b = base; b.t_off.resize(1); refuse(b); }                              // no targets
+	assert(align_plan(nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, pl) == -1); ++refused;
+	{ Batch b = base; b.o.flag = 0x100000; assert(b.plan(pl) == 0); }              // MM_F_FOR_ONLY is allowed
+	// seeded batches: slots, then the compact list and the DP plan from records a planning kernel could have left
+	std::mt19937 rng(11);
+	for (int t = 0; t < 30; ++t) {
+		Batch b;
+		const int n_t = 1 + rng() % 3;
+		std::vector<int> tl;
+		for (int i = 0; i < n_t; ++i) { tl.push_back(200 + rng() % 3000); b.target(tl.back()); }
+		const int n_reads = rng() % 6;
+		for (int r = 0; r < n_reads; ++r) {
+			const int qlen = 100 + rng() % 1500, rid = rng() % n_t, rev = rng() % 2, n_a = rng() % 40;
+			b.read(qlen);
+			for (int i = 0; i < n_a; ++i) b.anchor(rev, rid, rng() % tl[rid], rng() % qlen);
+			int as = 0;
+			while (as < n_a && rng() % 4) { const int cnt = rng() % (n_a - as + 1); b.region(as, cnt); as += cnt; }
+		}
+		assert(b.plan(pl) == 0);
+		assert((int64_t)pl.slot_off.size() == pl.n_regs + 1 && (int64_t)pl.reg_read.size() == pl.n_regs);
+		std::vector<AlignReg> reg((size_t)pl.n_regs);
+		std::vector<KswProb> slot((size_t)pl.n_slots);
+		for (int64_t g = 0; g < pl.n_regs; ++g) {
+			const int cnt = b.regs[(size_t)g * AL_REG_WORDS + 1];
+			assert(pl.slot_off[(size_t)g + 1] - pl.slot_off[(size_t)g] == (cnt ? cnt + 1 : 0));
+			reg[(size_t)g] = AlignReg{};
+			reg[(size_t)g].n_prob = cnt ? (int)(rng() % (cnt + 3)) - 1 : 0;        // also below 0 and above the room: clamped
+			for (int64_t s = pl.slot_off[(size_t)g]; s < pl.slot_off[(size_t)g + 1]; ++s)
+				slot[(size_t)s] = KswProb{0, 0, 0, (int32_t)(rng() % 400) - 5, (int32_t)(rng() % 400) - 5, (int32_t)(rng() % 100), 400, -1, (int32_t)(rng() % 2 ? 0x08 : 0x40)};
+		}
+		KswPlan kp;
+		std::vector<int32_t> src;
+		std::vector<int64_t> first;
+		int64_t n_bases = 0;
+		align_compact(pl, reg, slot, kp.prob, src, first, n_bases);
+		assert(first.size() == (size_t)pl.n_regs + 1 && first.back() == (int64_t)kp.prob.size() && src.size() == kp.prob.size());
+		int64_t at = 0;
+		for (size_t c = 0; c < kp.prob.size(); ++c) {
+			const KswProb &p = kp.prob[c];
+			assert(p.qlen >= 0 && p.tlen >= 0 && p.q_beg == at && p.t_beg == at + p.qlen && src[c] >= 0 && src[c] < pl.n_slots);
+			at += p.qlen + p.tlen;
+		}
+		assert(at == n_bases);
+		assert(ksw_plan_score(2, 4, 4, 2, 24, 1, kp.sc));
+		ksw_plan_route(kp, 256);
+		assert((int64_t)kp.order.size() == (int64_t)kp.prob.size() && kp.count[0] + kp.count[1] == (int64_t)kp.prob.size());
+		int64_t words = 0;
+		for (const KswProb &p : kp.prob) { assert(p.cig_beg == words); if (p.qlen > 0 && p.tlen > 0) words += p.qlen + p.tlen; }
+		assert(words == kp.cig_words);
+		++planned;
+	}
+	printf("align plan ok: %d batches planned, %d calls refused\n", planned, refused);
+	return 0;
+}
