@@ -1,5 +1,5 @@
-// chaindp_align_abi.cpp -- the region alignment stage of the host ABI (include/chaindp_align.h): mm_align1 for a batch of regions.
-// The checks and the layout of the problems are chaindp_align_plan.h's, the kernels align/chaindp_align.hip's, the DP chaindp_ksw_extd's own
+// chaindp_abi_align.cpp -- the region alignment stage of the host ABI (include/chaindp_align.h): mm_align1 for a batch of regions.
+// The checks and the layout of the problems are chaindp_align_plan.h's, the kernels chaindp_align.hip's, the DP chaindp_ksw_extd's own
 // (ksw_plan_route, ksw_reserve, ksw_dispatch); this file owns the buffers, the copies and the order of the launches:
 //   plan -> (lengths down, offsets up) -> gather -> DP -> zdrop -> (codes down) -> DP of the second pass -> stitch -> extra -> (counts down) -> pack
 #include "chaindp_ctx.h"

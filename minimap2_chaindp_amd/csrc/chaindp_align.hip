@@ -14,10 +14,10 @@
 // gathers, mm_reg_set_coor's sums, the inversion score and the per-base part of mm_update_extra run on all lanes.
 // Every base is fetched through a bounds check and every length is clamped to its sequence: where the reference would trip an assert the
 // answer is unspecified, but nothing is read or written outside a buffer.
-#include "../chaindp_kernels.h"
-#include "../chaindp_wave.h"
-#include "../chaindp_post_dev.h"
-#include "../chaindp_align_plan.h"
+#include "chaindp_kernels.h"
+#include "chaindp_wave.h"
+#include "chaindp_post_dev.h"
+#include "chaindp_align_plan.h"
 
 namespace chaindp {
 
