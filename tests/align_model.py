@@ -3,12 +3,16 @@ e != e2, on top of ksw_model.ksw_extd, plus the local-score model of ksw_ll_i16'
 proves both equal to the compiled reference on every case of tests/align_shapes.py before the goldens are trusted.
 
 A region is a dict of the REG_FIELDS (chaindp_reg_t / mm_reg1_t; `bits` is the bit-field word).  Anchors are two Python lists of
-ints (x, y of mm128_t) that align1 changes in place (MM_SEED_IGNORE).  Every branch the tests name is counted in `cover`."""
+ints (x, y of mm128_t) that align1 changes in place (MM_SEED_IGNORE).  Every branch the tests name is counted in `cover`, and every DP
+call is listed in `problems` as (kind, qlen, tlen, w, flag, pass): kind "left", "fill" or "right", pass 1 or 2.  The counters of the edge
+tier (tests/align_edge_shapes.py) say where a size falls relative to what the device kernels do 64 lanes, 64 bases or one launch at a
+time; none of them changes a result."""
 import collections
 
 import numpy as np
 
 import ksw_model as K
+import ksw_shapes as KS
 
 SEED_LONG_JOIN, SEED_IGNORE, SEED_TANDEM, SEED_SELF = 1 << 40, 1 << 41, 1 << 42, 1 << 43
 F_SPLICE, F_SR, F_FOR_ONLY, F_REV_ONLY = 0x80, 0x1000, 0x100000, 0x200000
@@ -22,6 +26,8 @@ EXTRA_FIELDS = ("has_extra", "dp_score", "dp_max", "n_ambi", "n_cigar")
 M64 = (1 << 64) - 1
 
 cover = collections.Counter()
+problems = []         # (kind, qlen, tlen, w, flag, pass) of every DP call, in the order align1 makes them
+ROUTE_NAMES = {KS.ROUTE_NONE: "none", KS.ROUTE_LDS: "lds", KS.ROUTE_GLOBAL: "global", KS.ROUTE_WIDE: "wide"}
 
 
 class Undefined(Exception):
@@ -256,17 +262,27 @@ def test_zdrop(opt, qseq, tseq, cigar, mat):
                 i += ln
             update(score, i, j)
     q_len, t_len = pos[1][1] - pos[1][0], pos[0][1] - pos[0][0]
+    if not opt["flag"] & (F_SPLICE | F_SR | F_FOR_ONLY | F_REV_ONLY) and max_zdrop > opt["zdrop_inv"] and not (q_len < opt["max_gap"] and t_len < opt["max_gap"]):
+        cover["inv_skipped_max_gap"] += 1
     if not opt["flag"] & (F_SPLICE | F_SR | F_FOR_ONLY | F_REV_ONLY) and max_zdrop > opt["zdrop_inv"] and q_len < opt["max_gap"] and t_len < opt["max_gap"]:
         qseq2 = revcomp(qseq[pos[1][0]:pos[1][1]])
         score = ll_score(qseq2, tseq[pos[0][0]:pos[0][1]], mat, opt["q"], opt["e"])
         cover["zdrop_inv_test"] += 1
         ll_seen.append((qseq2.copy(), np.array(tseq[pos[0][0]:pos[0][1]], np.uint8), score))
+        inv_seen.append((q_len, t_len, score))
+        cover["inv_t_le_64" if t_len <= 64 else "inv_t_65_128" if t_len <= 128 else "inv_t_gt_128"] += 1
+        if t_len % 64 < 2:
+            cover["inv_t_mod64_%d" % (t_len % 64)] += 1
+        if q_len != t_len:
+            cover["inv_q_gt_t" if q_len > t_len else "inv_q_lt_t"] += 1
         if score >= opt["min_chain_score"] * opt["a"] and score >= opt["min_dp_max"]:
             return 2
+        cover["inv_below_threshold"] += 1
     return 1 if max_zdrop > opt["zdrop"] else 0
 
 
 ll_seen = []          # (query, target, score) of every stretch test_zdrop gave to ll_score: the golden generator checks them against ksw_ll_i16
+inv_seen = []         # (q_len, t_len, score) of the same stretches
 
 
 def fix_cigar(r, cig, qseq, tseq):
@@ -334,24 +350,33 @@ def update_extra(r, p, qseq, tseq, mat, q, e):
     qseq, tseq = qseq[qshift:], tseq[tshift:]
     r["blen"] = r["mlen"] = 0
     toff = qoff = s = mx = 0
-    for c in p["cigar"]:
+    mx_at = None          # (index of the M op, offset in it) where the final dp_max was first reached
+    clamps = []           # (index of the M op, offset in it) of every clamp of s at 0 inside an M run
+    for k, c in enumerate(p["cigar"]):
         op, ln = c & 0xf, c >> 4
         if op == 0:
             cq, ct = qseq[qoff:qoff + ln].astype(np.int64), tseq[toff:toff + ln].astype(np.int64)
             ambi = (cq > 3) | (ct > 3)
             n_ambi, n_diff = int(ambi.sum()), int((~ambi & (cq != ct)).sum())
-            for v in mat[ct, cq]:
+            for l, v in enumerate(mat[ct, cq]):
                 s += int(v)
                 if s < 0:
                     s = 0
-                else:
-                    mx = max(mx, s)
+                    clamps.append((k, l))
+                elif s > mx:
+                    mx, mx_at = s, (k, l)
+            if ln in (64, 65, 128, 129):
+                cover["m_run_%d" % ln] += 1
             r["blen"] += ln - n_ambi; r["mlen"] += ln - (n_ambi + n_diff); p["n_ambi"] += n_ambi
             toff += ln; qoff += ln
         elif op in (1, 2):
             seq, off = (qseq, qoff) if op == 1 else (tseq, toff)
             n_ambi = int((seq[off:off + ln] > 3).sum())
             r["blen"] += ln - n_ambi; p["n_ambi"] += n_ambi
+            if n_ambi:
+                cover["n_ambi_in_gap"] += 1
+            if s - (q + e * ln) < 0:
+                cover["extra_gap_clamps"] += 1
             s = max(s - (q + e * ln), 0)
             if op == 1:
                 qoff += ln
@@ -362,6 +387,14 @@ def update_extra(r, p, qseq, tseq, mat, q, e):
     p["dp_max"] = mx
     if p["n_ambi"]:
         cover["n_ambi"] += 1
+    # offsets past the first 64-base block of an M run, where the device carries s and the maximum from one block to the next
+    for k, l in clamps:
+        if l >= 63 and l % 64 in (63, 0):
+            cover["extra_clamp_at_%d" % (l % 64)] += 1
+    if mx_at is not None and mx_at[1] >= 63 and mx_at[1] % 64 in (63, 0):
+        cover["extra_max_at_%d" % (mx_at[1] % 64)] += 1
+    if mx_at is not None and any(k == mx_at[0] and l // 64 < mx_at[1] // 64 for k, l in clamps):
+        cover["extra_clamp_then_max_later_block"] += 1
 
 
 def align1(opt, tcodes, qf, ax, ay, r, ksw=K.ksw_extd):
@@ -404,7 +437,26 @@ def align1(opt, tcodes, qf, ax, ay, r, ksw=K.ksw_extd):
             raise Undefined("r->p is NULL")
         return p
 
+    n_first_pass = 0
+
+    def dp(kind, pas, long_join, qseq, tseq, w, zdrop, end_bonus, flag):
+        nonlocal n_first_pass
+        problems.append((kind, len(qseq), len(tseq), w, flag, pas))
+        n_first_pass += pas == 1
+        route = ROUTE_NAMES[KS.expected_route(len(qseq), len(tseq), sc)]
+        cover["route_" + route] += 1
+        if route == "wide":
+            cover["route_wide_" + ("ext_" + kind if kind != "fill" else "long_join" if long_join else "fill_pass%d" % pas)] += 1
+        return ksw(qseq, tseq, *sc, w, zdrop, end_bonus, flag)
+
     as1, cnt1 = fix_bad_ends(r, ax, ay, opt["bw"], opt["min_chain_score"] * 2)
+    if cnt1 > 64:
+        cover["cnt1_gt_64"] += 1
+    if cnt1 > 128:
+        cover["cnt1_gt_128"] += 1
+    long_gaps = [i for i in range(1, cnt1) if abs(i32((i32(ay[as1 + i]) - i32(ay[as1 + i - 1])) - (i32(ax[as1 + i]) - i32(ax[as1 + i - 1])))) > 10]
+    if len(long_gaps) >= 2 and sum(i <= 64 for i in long_gaps) <= 1:       # the first 64-lane stride alone would count at most one
+        cover["long_gaps_only_past_64"] += 1
     filter_bad_seeds(as1, cnt1, ax, ay, 10, 40, opt["max_gap"] >> 1, 10)
     rs, qs = adjust_minier(opt, tcodes, qseq0, ax[as1], ay[as1])
     re, qe = adjust_minier(opt, tcodes, qseq0, ax[as1 + cnt1 - 1], ay[as1 + cnt1 - 1])
@@ -489,8 +541,8 @@ def align1(opt, tcodes, qf, ax, ay, r, ksw=K.ksw_extd):
     if qs > 0 and rs > 0:
         qseq = qseq0[rev][qs0:qs][::-1]
         tseq = tseq_all[rs0:rs][::-1]
-        ez, cig = ksw(qseq, tseq, *sc, bw, opt["zdrop_inv"] if split_inv_in else opt["zdrop"], opt["end_bonus"],
-                      EZ_EXTZ_ONLY | EZ_RIGHT | EZ_REV_CIGAR)
+        ez, cig = dp("left", 1, False, qseq, tseq, bw, opt["zdrop_inv"] if split_inv_in else opt["zdrop"], opt["end_bonus"],
+                     EZ_EXTZ_ONLY | EZ_RIGHT | EZ_REV_CIGAR)
         if len(cig):
             append(cig)
             p["dp_score"] += int(ez[0])
@@ -522,11 +574,12 @@ def align1(opt, tcodes, qf, ax, ay, r, ksw=K.ksw_extd):
             if qe < qs or re < rs:
                 raise Undefined("negative fill")
             qseq, tseq = qseq0[rev][qs:qe], tseq_all[rs:re]
-            ez, cig = ksw(qseq, tseq, *sc, bw1, opt["zdrop"], -1, EZ_APPROX_MAX)
+            long_join = bool(y & SEED_LONG_JOIN)
+            ez, cig = dp("fill", 1, long_join, qseq, tseq, bw1, opt["zdrop"], -1, EZ_APPROX_MAX)
             code = test_zdrop(opt, qseq, tseq, cig, mat)
             cover["zdrop_code_%d" % code] += 1
             if code:
-                ez, cig = ksw(qseq, tseq, *sc, bw1, opt["zdrop_inv"] if code == 2 else opt["zdrop"], -1, 0)
+                ez, cig = dp("fill", 2, long_join, qseq, tseq, bw1, opt["zdrop_inv"] if code == 2 else opt["zdrop"], -1, 0)
             append(cig)
             if ez[1]:
                 j = i - 1
@@ -540,6 +593,8 @@ def align1(opt, tcodes, qf, ax, ay, r, ksw=K.ksw_extd):
                     cover["drop_split"] += 1
                     if split_reg(r, r2, as1 + j + 1 - r["as"], qlen, ax, ay):
                         cover["drop_split_done"] += 1
+                        if r["cnt"] > 64 and r2["cnt"] > 64:
+                            cover["split_both_sides_gt_64"] += 1
                         if code == 2:
                             r2["bits"] |= BIT_SPLIT_INV
                             cover["drop_split_inv"] += 1
@@ -552,7 +607,7 @@ def align1(opt, tcodes, qf, ax, ay, r, ksw=K.ksw_extd):
             cover["skip_short"] += 1
 
     if not dropped and qe < qe0 and re < re0:
-        ez, cig = ksw(qseq0[rev][qe:qe0], tseq_all[re:re0], *sc, bw, opt["zdrop"], opt["end_bonus"], EZ_EXTZ_ONLY)
+        ez, cig = dp("right", 1, False, qseq0[rev][qe:qe0], tseq_all[re:re0], bw, opt["zdrop"], opt["end_bonus"], EZ_EXTZ_ONLY)
         if len(cig):
             append(cig)
             p["dp_score"] += int(ez[0])
@@ -565,6 +620,8 @@ def align1(opt, tcodes, qf, ax, ay, r, ksw=K.ksw_extd):
             cover["right_ext_to_target_end"] += 1
     if qe1 > qlen:
         raise Undefined("qe1 > qlen")
+    if n_first_pass == cnt0 + 1:          # every slot the device gives the region holds a problem
+        cover["slots_full"] += 1
     r["rs"], r["re"] = rs1, re1
     r["qs"], r["qe"] = (qlen - qe1, qlen - qs1) if rev else (qs1, qe1)
     if p is None:

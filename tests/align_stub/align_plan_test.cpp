@@ -124,6 +124,49 @@ int main()
 		assert(words == kp.cig_words);
 		++planned;
 	}
-	printf("align plan ok: %d batches planned, %d calls refused\n", planned, refused);
+	// more regions than the 65 536 workgroups a bookkeeping kernel gets: the plan and the compact list of 70 000 regions of two anchors
+	// (three slots each), the records' n_prob running over -1 .. 3 with one region that fills its slots exactly and one whose record
+	// claims more than its room, which is clamped to the room
+	const int big = 70000;
+	{
+		Batch b;
+		b.target(5000);
+		for (int r = 0; r < big; ++r) {
+			b.read(50);
+			b.anchor(r & 1, 0, 100 + r % 4000, 14); b.anchor(r & 1, 0, 125 + r % 4000, 39);
+			b.region(0, 2);
+		}
+		assert(b.plan(pl) == 0 && pl.n_regs == big && pl.n_slots == 3 * (int64_t)big && pl.n_anchors == 2 * (int64_t)big && pl.n_bases == 50 * (int64_t)big);
+		std::vector<AlignReg> reg((size_t)big, AlignReg{});
+		std::vector<KswProb> slot((size_t)pl.n_slots);
+		for (int g = 0; g < big; ++g) {
+			assert(pl.slot_off[(size_t)g] == 3 * (int64_t)g && pl.reg_read[(size_t)g] == g);
+			reg[(size_t)g].n_prob = g % 5 - 1;
+		}
+		const int full = 100, over = 66000;
+		reg[full].n_prob = 3; reg[over].n_prob = 3 + 4;
+		for (size_t s = 0; s < slot.size(); ++s) slot[s] = KswProb{0, 0, 0, (int32_t)(s % 40), (int32_t)(s % 37), 61, 400, -1, 0x08};
+		KswPlan kp;
+		std::vector<int32_t> src;
+		std::vector<int64_t> first;
+		int64_t n_bases = 0, at = 0;
+		align_compact(pl, reg, slot, kp.prob, src, first, n_bases);
+		assert(first.size() == (size_t)big + 1 && first.back() == (int64_t)kp.prob.size() && src.size() == kp.prob.size());
+		for (int g = 0; g < big; ++g) {
+			const int want = g == full || g == over ? 3 : std::min(std::max(g % 5 - 1, 0), 3);
+			assert(first[(size_t)g + 1] - first[(size_t)g] == want);
+			for (int64_t c = first[(size_t)g]; c < first[(size_t)g + 1]; ++c) assert(src[(size_t)c] == 3 * g + (int)(c - first[(size_t)g]));
+		}
+		for (size_t c = 0; c < kp.prob.size(); ++c) {
+			const KswProb &p = kp.prob[c];
+			assert(p.q_beg == at && p.t_beg == at + p.qlen && p.qlen == src[c] % 40 && p.tlen == src[c] % 37);
+			at += p.qlen + p.tlen;
+		}
+		assert(at == n_bases);
+		assert(ksw_plan_score(2, 4, 4, 2, 24, 1, kp.sc));
+		ksw_plan_route(kp, 256);
+		assert(kp.order.size() == kp.prob.size() && kp.count[0] == (int64_t)kp.prob.size() && kp.count[1] == 0 && kp.grid[0] <= 256 * 32);
+	}
+	printf("align plan ok: %d batches planned, %d calls refused; %d regions compacted, full and overfull slots clamped\n", planned, refused, big);
 	return 0;
 }
