@@ -430,4 +430,5 @@ int chaindp_set_variant(chaindp_ctx_t *ctx, int force_general);
 /* base-level alignment, the dual-gap extension DP (chaindp_ksw_extd): part of this ABI, declared in a header of its own */
 #include "chaindp_ksw.h"
 #include "chaindp_align.h"
+#include "chaindp_align_inv.h"
 #endif

@@ -31,6 +31,8 @@ KSW_SCORE_ONLY, KSW_RIGHT, KSW_APPROX_MAX, KSW_EXTZ_ONLY, KSW_REV_CIGAR = 0x01, 
 KSW_EZ_FIELDS = ("max", "zdropped", "max_q", "max_t", "mqe", "mqe_t", "mte", "mte_q", "score", "reach_end")
 # ... and for mm_align1
 ALIGN_SYMBOLS = tuple(_cabi.prototypes("chaindp_align.h"))
+# ... and for mm_align1_inv
+ALIGN_INV_SYMBOLS = tuple(_cabi.prototypes("chaindp_align_inv.h"))
 ALIGN_EXTRA_DTYPE = np.dtype([(k, "<i4") for k in ("has_extra", "dp_score", "dp_max", "n_ambi", "n_cigar")])   # chaindp_align_extra_t
 ERR_CAPACITY = -2
 
@@ -47,14 +49,14 @@ _lib = None
 
 
 def lib():
-    """The library, every function of include/chaindp.h, chaindp_gaps.h, chaindp_ksw.h, chaindp_align.h and chaindp_debug.h bound with the
+    """The library, every function of include/chaindp.h, chaindp_gaps.h, chaindp_ksw.h, chaindp_align.h, chaindp_align_inv.h and chaindp_debug.h bound with the
     header's prototype."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise ChainDPError(f"{LIB_PATH} is missing: build it with __graft_entry__.build() "
                                "(make -C minimap2_chaindp_amd/csrc); there is no fallback path")
-        _lib = _cabi.bind(C.CDLL(LIB_PATH), "chaindp.h", "chaindp_gaps.h", "chaindp_ksw.h", "chaindp_align.h", "chaindp_debug.h")
+        _lib = _cabi.bind(C.CDLL(LIB_PATH), "chaindp.h", "chaindp_gaps.h", "chaindp_ksw.h", "chaindp_align.h", "chaindp_align_inv.h", "chaindp_debug.h")
     return _lib
 
 
@@ -112,6 +114,7 @@ _CAPS = {
     "map_frag_seqs": _Cap("n_bases", 16, True,  "raise", "again",      "before"),  # again: the flip is part of the call
     # align1: the room is for CIGAR words, not hits; a guess of one word per four read bases, the whole call again with the exact count
     "align1":        _Cap("n_bases", 4,  True,  "raise", "again",      None),
+    "align1_inv":    _Cap("n_bases", 4,  True,  "raise", "again",      None),      # the same for the inversions' CIGAR words
 }
 
 
@@ -598,6 +601,49 @@ class Device:
                 raise err
             self._check(rc)
             return a_out, regs_out, r2, extra, off, cigar[:int(off[-1])]
+
+    def align1_inv(self, opt, seq_off, seq, regs_off, regs, cigar_cap=None):
+        """mm_align1_inv for every pair of neighbouring regions of every read (chaindp_align1_inv), after all align1 rounds: regs REG_DTYPE in
+        mm_align_skeleton's order, what regs2 split off inserted behind its region, no inversion records among them.  Slot g (region i >= 1
+        of its read) is the pair (i - 1, i).  Returns (made int32[n_regions], r_inv REG_DTYPE[n_regions], extra ALIGN_EXTRA_DTYPE[n_regions],
+        cigar_off int64[n_regions + 1], cigar uint32[...]); made: 0 no test, 1 made, 2 below min_dp_max, 3 not tested because the pair before
+        it was made, 4 no CIGAR.  cigar_cap as align1's; a cap of the caller's that is too small raises ChainDPError with err.made /
+        .r_inv / .extra / .cigar_off holding what the C call filled in."""
+        seq_off, regs_off = _arr(seq_off, np.int64), _arr(regs_off, np.int64)
+        seq = np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else _arr(seq, np.uint8)
+        regs_in = _arr(regs, REG_DTYPE)
+        n_reads, n_regs = len(seq_off) - 1, len(regs_in)
+        if len(regs_off) != n_reads + 1 or int(regs_off[-1]) != n_regs or int(seq_off[-1]) != len(seq):
+            raise ValueError("seq_off and regs_off need one entry per read and one more, and must end at the sizes of seq and regs")
+        row = _CAPS["align1_inv"]
+        cap = int(cigar_cap) if cigar_cap is not None else max(len(seq) // row.divisor, REGS_CAP_FLOOR if row.floored else 1)
+        while True:
+            made, r_inv, extra = np.zeros(n_regs, np.int32), np.zeros(n_regs, REG_DTYPE), np.zeros(n_regs, ALIGN_EXTRA_DTYPE)
+            off, cigar = np.zeros(n_regs + 1, np.int64), np.zeros(max(cap, 1), np.uint32)
+            rc = self._lib.chaindp_align1_inv(self._ctx, C.byref(opt), n_reads, _ptr(seq_off), _ptr0(seq), _ptr(regs_off), _ptr0(regs_in), _ptr0(made),
+                                              _ptr0(r_inv), _ptr0(extra), _ptr(off), _ptr(cigar) if cap > 0 else None, max(cap, 0))
+            short = rc == ERR_CAPACITY and int(off[-1]) > cap >= 0
+            if short and cigar_cap is None and row.retry == "again":
+                cap = int(off[-1])
+                continue
+            if short:
+                err = ChainDPError(f"chaindp error {rc}: {self._lib.chaindp_last_error(self._ctx).decode()}")
+                err.made, err.r_inv, err.extra, err.cigar_off = made, r_inv, extra, off
+                raise err
+            self._check(rc)
+            return made, r_inv, extra, off, cigar[:int(off[-1])]
+
+    def align_inv_ll(self, n):
+        """score, qe, te of ksw_ll_i16 for the n candidate pairs of the last align1_inv, on the reversed stretches (test hook): int32[n, 3]."""
+        out = np.zeros((max(int(n), 1), 3), np.int32)
+        self._check(self._lib.chaindp_align_inv_debug_ll(self._ctx, int(n), _ptr(out)))
+        return out[:int(n)]
+
+    def align_inv_ms(self):
+        """Device milliseconds of the last align1_inv made while profiling was on (tuning hook): dict of ll, dp, finish, pack."""
+        ms = (C.c_double * 4)()
+        self._check(self._lib.chaindp_align_inv_debug_ms(self._ctx, ms))
+        return dict(zip(("ll", "dp", "finish", "pack"), (float(x) for x in ms)))
 
     def align_ms(self):
         """Device milliseconds of the last align1 made while profiling was on (tuning hook): dict of plan, dp, zdrop, stitch, extra."""

@@ -106,6 +106,11 @@ struct chaindp_ctx {
 	chaindp::DevGrow al_tgt, al_toff, al_in, al_reg, al_slot, al_side, al_ez1, al_cig1, al_code, al_stage, al_res, al_out;
 	std::vector<int64_t> al_t_off;             // the resident targets' offsets (host copy); empty: none set
 	double al_ms[5] = {-1, -1, -1, -1, -1};    // plan, DP, zdrop, stitch, extra of the last chaindp_align1 made while profiling was on
+	// mm_align1_inv, chaindp_align1_inv (allocated on first use, grown with the batch): the reads and regions of the batch with the
+	// candidate list; the per-slot results; the local scores, survivors and their problems; the packed CIGARs
+	chaindp::DevGrow inv_in, inv_res, inv_ll, inv_out;
+	int64_t inv_n = -1;                        // candidates of the last chaindp_align1_inv whose local scores are resident (chaindp_align_inv_debug_ll)
+	double inv_ms[4] = {-1, -1, -1, -1};       // local score, gather + DP, finish + skip, pack of the last call made while profiling was on
 	int frag_lds_cap = FRAG_LDS_CAP;           // chaindp_debug_set_frag_lds_cap (tests): fewer hits per fragment stay in LDS
 	// sketch (allocated on first use, grown with the batch)
 	chaindp::SketchArgs sk = {};

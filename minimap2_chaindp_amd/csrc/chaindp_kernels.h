@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include "chaindp_ksw_plan.h"
 #include "chaindp_align_plan.h"
+#include "chaindp_inv_plan.h"
 
 namespace chaindp {
 
@@ -379,6 +380,23 @@ hipError_t launch_align_stitch(hipStream_t st, const AlignOpt &o, const AlignDev
                                const uint32_t *d_cig2);
 hipError_t launch_align_extra(hipStream_t st, const AlignOpt &o, const AlignDev &d);
 hipError_t launch_align_pack(hipStream_t st, const AlignDev &d, const int64_t *d_off, uint32_t *d_out);
+
+// mm_align1_inv between two split regions (align.c:638-693): inv/chaindp_inv.hip.  One wave per candidate pair (the compact list of
+// chaindp_inv_plan.h) or per survivor of min_dp_max; made, r_inv and extra are per slot (region) and zero where nothing was made.
+struct InvDev {
+	int64_t n_reads; int n_cand, n_surv;
+	const int64_t *regs_off, *seq_off; const char *seq;
+	const int64_t *t_off; const uint8_t *tcodes;    // the resident targets
+	const InvCand *cand; const int32_t *slot_cand;
+	const InvSurv *surv; const KswProb *prob;       // the survivors and their extension problems
+	int32_t *made, *r_inv, *extra;
+};
+// lds_rows: rows of the padded query of the longest query stretch (4 bytes of LDS each)
+hipError_t launch_inv_ll(hipStream_t st, const AlignOpt &o, const InvDev &d, int lds_rows, int32_t *d_out3);
+hipError_t launch_inv_gather(hipStream_t st, const InvDev &d, uint8_t *d_bases);
+hipError_t launch_inv_finish(hipStream_t st, const AlignOpt &o, const InvDev &d, const int32_t *d_ez, uint32_t *d_cig);
+hipError_t launch_inv_skip(hipStream_t st, const InvDev &d);
+hipError_t launch_inv_pack(hipStream_t st, const InvDev &d, const int64_t *d_off, const uint32_t *d_cig, uint32_t *d_out);
 
 } // namespace chaindp
 #endif
