@@ -54,6 +54,13 @@ int chaindp_ksw_debug_routing(int64_t out[6]);
 /* The route every problem of the last chaindp_ksw_extd (n of them) took, as the device reported it: 0 the reference's early return,
  * 1 state in LDS, 2 state in global scratch, 3 state in LDS and several waves. */
 int chaindp_ksw_debug_route(chaindp_ctx_t *ctx, int64_t n, int32_t *route);
+/* Launches nothing.  cap > 0: every later plan of the DP (chaindp_ksw_extd, chaindp_align1, chaindp_align1_inv) launches at most cap
+ * workgroups of either kind, so that a workgroup takes problem after problem; 0 (the default) leaves the plan alone; negative is
+ * CHAINDP_ERR_ARG. */
+int chaindp_ksw_debug_set_grid_cap(chaindp_ctx_t *ctx, int cap);
+/* Launches nothing.  The last plan of the DP on this context: out = the problems of the one-wave and of the several-wave launch, their
+ * workgroups, the LDS bytes of state each workgroup of them asked for, the bytes of each one's slice of path matrix.  All 0 before. */
+int chaindp_ksw_debug_launch(chaindp_ctx_t *ctx, int64_t out[8]);
 /* Device milliseconds of the DP kernel in the last chaindp_ksw_extd made while profiling was on (chaindp_set_profiling); -1 before. */
 double chaindp_ksw_debug_ms(chaindp_ctx_t *ctx);
 

@@ -658,6 +658,17 @@ class Device:
         self._check(self._lib.chaindp_ksw_debug_route(self._ctx, int(n), _ptr(route)))
         return route[:int(n)]
 
+    def ksw_set_grid_cap(self, cap=0):
+        """Test hook: every later DP plan (ksw_extd, align1, align1_inv) launches at most `cap` workgroups of either kind; 0: the plan's own."""
+        self._check(self._lib.chaindp_ksw_debug_set_grid_cap(self._ctx, int(cap)))
+
+    def ksw_launch(self):
+        """The last DP plan of this context (test hook): dict of count, grid, lds_bytes, path_stride, each a pair (the one-wave launch,
+        the several-wave launch)."""
+        out = (C.c_int64 * 8)()
+        self._check(self._lib.chaindp_ksw_debug_launch(self._ctx, out))
+        return {k: (int(out[2 * i]), int(out[2 * i + 1])) for i, k in enumerate(("count", "grid", "lds_bytes", "path_stride"))}
+
     def ksw_ms(self):
         """Device milliseconds of the DP kernel in the last ksw_extd made while profiling was on (tuning hook); -1 before."""
         return float(self._lib.chaindp_ksw_debug_ms(self._ctx))

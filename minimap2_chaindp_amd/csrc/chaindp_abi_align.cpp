@@ -162,7 +162,7 @@ extern "C" int chaindp_align1(chaindp_ctx_t *ctx, const chaindp_align_opt_t *opt
 	std::vector<int64_t> first;
 	int64_t n_bases = 0;
 	align_compact(ap, areg, slots, p1.prob, src_slot, first, n_bases);
-	ksw_plan_route(p1, ctx->dp.cus);
+	ksw_plan_route(p1, ctx->dp.cus, ctx->ksw_grid_cap);
 	const size_t P = p1.prob.size();
 	d.n_prob = (int64_t)P;
 	if ((rc = ksw_reserve(ctx, p1, n_bases, WHO))) return rc;
@@ -209,7 +209,7 @@ extern "C" int chaindp_align1(chaindp_ctx_t *ctx, const chaindp_align_opt_t *opt
 		}
 		HIP_TRY(ctx, hipMemcpyAsync(d_pc + o_sec, sec.data(), P * 4, hipMemcpyHostToDevice, st));
 		if (!p2.prob.empty()) {
-			ksw_plan_route(p2, ctx->dp.cus);
+			ksw_plan_route(p2, ctx->dp.cus, ctx->ksw_grid_cap);
 			if ((rc = ksw_reserve(ctx, p2, n_bases, WHO))) return rc;
 			HIP_TRY(ctx, mark(-1));
 			if ((rc = ksw_dispatch(ctx, p2, nullptr, nullptr))) return rc;

@@ -129,7 +129,7 @@ extern "C" int chaindp_align1_inv(chaindp_ctx_t *ctx, const chaindp_align_opt_t 
 	const size_t S = surv.size();
 	d.n_surv = (int)S;
 	if (S) {
-		ksw_plan_route(kp, ctx->dp.cus);
+		ksw_plan_route(kp, ctx->dp.cus, ctx->ksw_grid_cap);
 		if ((rc = ksw_reserve(ctx, kp, n_bases, WHO))) return rc;
 		HIP_TRY(ctx, up(d_ll, o_surv, surv.data(), S * sizeof(InvSurv)));
 		HIP_TRY(ctx, up(d_ll, o_prob, kp.prob.data(), S * sizeof(KswProb)));

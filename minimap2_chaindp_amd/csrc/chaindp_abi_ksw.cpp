@@ -27,6 +27,10 @@ int chaindp::ksw_reserve(chaindp_ctx *ctx, const KswPlan &pl, int64_t n_bases, c
 	if ((rc = ksw_grow(ctx, ctx->ksw_path, (size_t)pl.grid[0] * pl.path_stride[0] + (size_t)pl.grid[1] * pl.path_stride[1] + 16, "path matrices", who))) return rc;
 	if ((rc = ksw_grow(ctx, ctx->ksw_cig, (size_t)pl.cig_words * sizeof(uint32_t) + 16, "CIGAR staging", who))) return rc;
 	ctx->ksw_n = 0;
+	for (int c = 0; c < 2; ++c) {                        // chaindp_ksw_debug_launch
+		ctx->ksw_launch[c] = pl.count[c]; ctx->ksw_launch[2 + c] = pl.grid[c];
+		ctx->ksw_launch[4 + c] = (int64_t)pl.lds_bytes[c]; ctx->ksw_launch[6 + c] = (int64_t)pl.path_stride[c];
+	}
 	return CHAINDP_OK;
 }
 
@@ -63,7 +67,7 @@ extern "C" int chaindp_ksw_extd(chaindp_ctx_t *ctx, int64_t n, const uint8_t *ba
 	if (!cigar_off || (n > 0 && !ez_out)) { ctx->err = "chaindp_ksw_extd: NULL output array"; return CHAINDP_ERR_ARG; }
 	if (cigar_cap < 0 || (cigar_cap > 0 && !cigar)) { ctx->err = "chaindp_ksw_extd: cigar_cap without a cigar array"; return CHAINDP_ERR_ARG; }
 	KswPlan pl;
-	if (ksw_plan(n, bases, q_beg, q_len, t_beg, t_len, a, b, q, e, q2, e2, w, zdrop, end_bonus, flag, ctx->dp.cus, pl)) {
+	if (ksw_plan(n, bases, q_beg, q_len, t_beg, t_len, a, b, q, e, q2, e2, w, zdrop, end_bonus, flag, ctx->dp.cus, pl, ctx->ksw_grid_cap)) {
 		ctx->err = pl.err;
 		return CHAINDP_ERR_ARG;
 	}
@@ -132,6 +136,25 @@ extern "C" int chaindp_ksw_debug_routing(int64_t out[6])
 
 // tuning hook: device milliseconds of k_ksw_extd in the last chaindp_ksw_extd made while profiling was on (chaindp_set_profiling); -1 before
 extern "C" double chaindp_ksw_debug_ms(chaindp_ctx_t *ctx) { return ctx ? ctx->ksw_ms : -1; }
+
+// test hook: at most cap workgroups in either DP launch of every later plan (chaindp_ksw_extd, chaindp_align1, chaindp_align1_inv), so
+// that a workgroup takes problem after problem; 0 leaves the plan alone.  Launches nothing.
+extern "C" int chaindp_ksw_debug_set_grid_cap(chaindp_ctx_t *ctx, int cap)
+{
+	if (!ctx) return CHAINDP_ERR_ARG;
+	if (cap < 0) { ctx->err = "chaindp_ksw_debug_set_grid_cap: negative cap"; return CHAINDP_ERR_ARG; }
+	ctx->ksw_grid_cap = cap;
+	return CHAINDP_OK;
+}
+
+// test hook: the last plan the DP's buffers were sized for -- count[0..1], grid[0..1], lds_bytes[0..1], path_stride[0..1].  Launches nothing.
+extern "C" int chaindp_ksw_debug_launch(chaindp_ctx_t *ctx, int64_t out[8])
+{
+	if (!ctx) return CHAINDP_ERR_ARG;
+	if (!out) { ctx->err = "chaindp_ksw_debug_launch: NULL out"; return CHAINDP_ERR_ARG; }
+	memcpy(out, ctx->ksw_launch, sizeof ctx->ksw_launch);
+	return CHAINDP_OK;
+}
 
 // test hook: the route every problem of the last chaindp_ksw_extd took, as the device reported it (0 early return, 1 LDS, 2 global, 3 LDS with several waves)
 extern "C" int chaindp_ksw_debug_route(chaindp_ctx_t *ctx, int64_t n, int32_t *route)

@@ -99,6 +99,8 @@ struct chaindp_ctx {
 	// CSR offsets and result words; the workgroups' slices of DP state (global route) and of path matrix; CIGARs as left and as packed
 	chaindp::DevGrow ksw_bases, ksw_prob, ksw_ez, ksw_state, ksw_path, ksw_cig, ksw_out;
 	double ksw_ms = -1;                        // k_ksw_extd's device time in the last call made while profiling was on
+	int ksw_grid_cap = 0;                      // chaindp_ksw_debug_set_grid_cap: at most so many workgroups per DP launch (0: the plan's own)
+	int64_t ksw_launch[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the last plan ksw_reserve saw: count, grid, lds_bytes, path_stride of the two launches (chaindp_ksw_debug_launch)
 	int64_t ksw_n = -1;                        // problems of the last chaindp_ksw_extd whose results are resident (chaindp_ksw_debug_route)
 	// mm_align1, chaindp_align1 (allocated on first use, grown with the batch): the targets' codes and offsets; the reads, anchors and
 	// regions of the batch with their offsets; the regions' plans, problem slots and side records; the first pass's results and CIGARs

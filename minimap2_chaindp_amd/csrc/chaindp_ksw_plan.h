@@ -69,8 +69,9 @@ struct KswPlan {
 #define KSW_PATH_TOTAL ((size_t)1 << 32)    // the path slices of a launch's workgroups together stay below this while there are 64 or more
 
 // From the records in pl.prob (lengths, band, flag; pl.sc set): cig_beg of every problem, the order, the two launches' sizes.
-// cus: compute units of the device.  What chaindp_align1 calls on the records its planning kernel made.
-inline void ksw_plan_route(KswPlan &pl, int cus)
+// cus: compute units of the device; grid_cap > 0: no launch gets more workgroups than that (chaindp_ksw_debug_set_grid_cap).
+// What chaindp_align1 calls on the records its planning kernel made.
+inline void ksw_plan_route(KswPlan &pl, int cus, int grid_cap = 0)
 {
 	const int64_t n = (int64_t)pl.prob.size();
 	std::vector<int64_t> work((size_t)n);
@@ -108,6 +109,7 @@ inline void ksw_plan_route(KswPlan &pl, int cus)
 		int per_cu = (int)std::min<size_t>(32 / waves, lds_cu / lds);
 		if (per_cu < 1) per_cu = 1;
 		pl.grid[c] = (int)std::min<int64_t>(pl.count[c], (int64_t)(cus > 0 ? cus : 1) * per_cu);
+		if (grid_cap > 0) pl.grid[c] = std::min(pl.grid[c], grid_cap);
 	}
 	// ... fewer while the launch's path slices together would pass KSW_PATH_TOTAL
 	for (int c = 0; c < 2; ++c)
@@ -125,10 +127,10 @@ inline bool ksw_plan_score(int a, int b, int q, int e, int q2, int e2, KswScore 
 	return true;
 }
 
-// 0 and a filled plan, or -1 (CHAINDP_ERR_ARG) with plan.err.  cus: compute units of the device.
+// 0 and a filled plan, or -1 (CHAINDP_ERR_ARG) with plan.err.  cus, grid_cap: as ksw_plan_route takes them.
 inline int ksw_plan(int64_t n, const uint8_t *bases, const int64_t *q_beg, const int32_t *q_len, const int64_t *t_beg, const int32_t *t_len,
                     int a, int b, int q, int e, int q2, int e2, const int32_t *w, const int32_t *zdrop, const int32_t *end_bonus,
-                    const int32_t *flag, int cus, KswPlan &pl)
+                    const int32_t *flag, int cus, KswPlan &pl, int grid_cap = 0)
 {
 	pl = KswPlan();
 	if (n < 0) { pl.err = "chaindp_ksw_extd: negative problem count"; return -1; }
@@ -153,7 +155,7 @@ inline int ksw_plan(int64_t n, const uint8_t *bases, const int64_t *q_beg, const
 		for (int64_t k = 0; k < p.qlen; ++k) if (bases[p.q_beg + k] > 4) { pl.err = "chaindp_ksw_extd: base above 4 in the query of problem " + std::to_string(i); return -1; }
 		for (int64_t k = 0; k < p.tlen; ++k) if (bases[p.t_beg + k] > 4) { pl.err = "chaindp_ksw_extd: base above 4 in the target of problem " + std::to_string(i); return -1; }
 	}
-	ksw_plan_route(pl, cus);
+	ksw_plan_route(pl, cus, grid_cap);
 	return 0;
 }
 

@@ -15,14 +15,14 @@ struct Batch {
 	std::vector<int64_t> q_beg, t_beg;
 	std::vector<int32_t> q_len, t_len, w, zdrop, end_bonus, flag;
 	int sc[6] = {2, 4, 4, 2, 24, 1};
-	int plan(KswPlan &pl, int cus = 256) const
+	int plan(KswPlan &pl, int cus = 256, int cap = 0) const
 	{
 		// copies of exactly the stated sizes (an empty vector's data() may be anything: NULL is what a caller passes then)
 		auto exact = [](const auto &v) { using T = typename std::decay<decltype(v[0])>::type; std::unique_ptr<T[]> p(new T[v.size()]); std::copy(v.begin(), v.end(), p.get()); return p; };
 		auto b = exact(bases); auto qb = exact(q_beg); auto tb = exact(t_beg); auto ql = exact(q_len); auto tl = exact(t_len);
 		auto w_ = exact(w); auto z = exact(zdrop); auto eb = exact(end_bonus); auto f = exact(flag);
 		return ksw_plan((int64_t)q_len.size(), bases.empty() ? nullptr : b.get(), qb.get(), ql.get(), tb.get(), tl.get(), sc[0], sc[1], sc[2], sc[3], sc[4], sc[5],
-		                w_.get(), z.get(), eb.get(), f.get(), cus, pl);
+		                w_.get(), z.get(), eb.get(), f.get(), cus, pl, cap);
 	}
 	void add(std::mt19937 &rng, int ql, int tl, int w_, int flag_)
 	{
@@ -64,7 +64,7 @@ static void check_problem(const KswPlan &pl, const KswProb &p, int64_t cig_end)
 	}
 }
 
-static void check_plan(const Batch &b, const KswPlan &pl, int cus)
+static void check_plan(const Batch &b, const KswPlan &pl, int cus, int cap = 0)
 {
 	const size_t n = b.q_len.size();
 	assert(pl.prob.size() == n && pl.order.size() == n && (size_t)(pl.count[0] + pl.count[1]) == n);
@@ -86,6 +86,7 @@ static void check_plan(const Batch &b, const KswPlan &pl, int cus)
 		assert((pl.grid[c] > 0) == (pl.count[c] > 0) && pl.grid[c] <= pl.count[c] && pl.grid[c] <= cus * 32);
 		assert(pl.path_stride[c] % 256 == 0 && pl.lds_bytes[c] <= KSW_LDS_BUDGET);
 		assert(pl.grid[c] <= 64 || (size_t)pl.grid[c] * pl.path_stride[c] <= KSW_PATH_TOTAL);
+		if (cap > 0) assert(pl.grid[c] <= cap);                       // chaindp_ksw_debug_set_grid_cap
 	}
 	assert(pl.state_stride % 256 == 0);
 }
@@ -94,7 +95,7 @@ int main()
 {
 	std::mt19937 rng(12345);
 	KswPlan pl;
-	int refused = 0, planned = 0;
+	int refused = 0, planned = 0, capped = 0;
 	// the empty call
 	{ Batch b; assert(b.plan(pl) == 0 && pl.prob.empty() && pl.grid[0] == 0 && pl.grid[1] == 0 && pl.cig_words == 0); }
 	// refusals: each leaves a message and reads nothing it should not
@@ -134,7 +135,49 @@ int main()
 		assert(pl.sc.q + pl.sc.e <= pl.sc.q2 + pl.sc.e2 && pl.sc.qe0 == b.sc[2] + b.sc[3]);
 		check_plan(b, pl, cus);
 		++planned;
+		// the grid cap: no launch above it, every size as before; cap 1 is one workgroup for the whole launch
+		const int grid0[2] = {pl.grid[0], pl.grid[1]};
+		for (int cap : {1, 3, 1 << 20}) {
+			KswPlan pc;
+			assert(b.plan(pc, cus, cap) == 0);
+			check_plan(b, pc, cus, cap);
+			for (int c = 0; c < 2; ++c) assert(pc.grid[c] == std::min(grid0[c], cap) && pc.path_stride[c] == pl.path_stride[c] && pc.lds_bytes[c] == pl.lds_bytes[c]);
+			assert(pc.order == pl.order && pc.cig_words == pl.cig_words && pc.state_stride == pl.state_stride);
+			++capped;
+		}
 	}
-	printf("ksw plan ok: %d batches planned, %d calls refused\n", planned, refused);
+	// the shapes of the edge tier (tests/ksw_edge_shapes.py): one and two bases against the wide and global routes, the long queries
+	{
+		Batch b;
+		const int shapes[][3] = {{1, 700, -1}, {2, 690, -1}, {7793, 17, -1}, {7793, 17, 5}, {1, 5500, -1}, {2, 5470, -1}, {3000, 5500, 100}, {5480, 5500, 20},
+		                         {300, 5600, -1}, {64, 5470, 70}, {600, 610, 1}, {3000, 640, 8}, {100, 1500, 60}};
+		for (const auto &s : shapes) for (int f : {0, 0x01, 0xc2}) b.add(rng, s[0], s[1], s[2], f);
+		for (int cap : {0, 1, 2}) { assert(b.plan(pl, 256, cap) == 0); check_plan(b, pl, 256, cap); ++capped; }
+	}
+	// the halving of the grid: 65 to 400 one-wave problems, one of them global with a path matrix of 32 to 128 MiB -- that many slices
+	// of that size pass KSW_PATH_TOTAL, so the grid comes out below min(count, cus * per_cu)
+	int halved = 0;
+	for (int n : {65, 66, 127, 128, 129, 200, 400}) {
+		Batch b;
+		int big;                                                        // 7 999 x 4 016 = 32 MiB .. 15 999 x 8 016 = 128 MiB
+		do big = 4000 + (int)(rng() % 4001); while ((size_t)n * (size_t)(2 * big - 1) * (size_t)ksw_n_col(big, big, -1) <= KSW_PATH_TOTAL + ((size_t)n << 8));
+		const int at = (int)(rng() % n);
+		for (int i = 0; i < n; ++i) {
+			if (i == at) b.add(rng, big, big, -1, 0x40);
+			else b.add(rng, lens[1 + rng() % 13], lens[1 + rng() % 13], ws[rng() % 12], flags[rng() % 9]);
+		}
+		assert(b.plan(pl) == 0);
+		check_plan(b, pl, 256);
+		const size_t path = (size_t)(2 * big - 1) * (size_t)ksw_n_col(big, big, -1);
+		assert(path >= ((size_t)32 << 20) - 4096 * 16 && path <= (size_t)128 << 20 && pl.path_stride[0] == (path + 255) / 256 * 256);
+		assert(pl.count[0] == n && pl.count[1] == 0);
+		assert((size_t)n * pl.path_stride[0] > KSW_PATH_TOTAL);            // ... so the loop had to run
+		assert(pl.grid[0] < n && pl.grid[0] >= 32 && pl.grid[0] <= 64);      // n < cus * per_cu: the natural grid would have been n
+		KswPlan pc;                                                     // the cap comes first: a capped grid of 64 or less is not halved
+		assert(b.plan(pc, 256, 3) == 0 && pc.grid[0] == 3);
+		check_plan(b, pc, 256, 3);
+		++halved;
+	}
+	printf("ksw plan ok: %d batches planned, %d calls refused; %d plans under a grid cap, %d with a halved grid\n", planned, refused, capped, halved);
 	return 0;
 }

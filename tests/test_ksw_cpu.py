@@ -97,7 +97,8 @@ def test_fixtures_cover_what_the_issue_lists():
 def test_header_binds_through_cabi():
     from minimap2_chaindp_amd import _cabi, chaindp
     protos = _cabi.prototypes("chaindp_ksw.h")
-    assert list(protos) == ["chaindp_ksw_extd", "chaindp_ksw_debug_routing", "chaindp_ksw_debug_route", "chaindp_ksw_debug_ms"]
+    assert list(protos) == ["chaindp_ksw_extd", "chaindp_ksw_debug_routing", "chaindp_ksw_debug_route", "chaindp_ksw_debug_set_grid_cap",
+                            "chaindp_ksw_debug_launch", "chaindp_ksw_debug_ms"]
     assert chaindp.KSW_SYMBOLS == tuple(protos)
     restype, argtypes = protos["chaindp_ksw_extd"]
     assert restype is C.c_int and len(argtypes) == 21
