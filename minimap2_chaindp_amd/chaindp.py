@@ -112,9 +112,10 @@ _CAPS = {
     "frag_post":     _Cap("total",   4,  True,  "raise", "again",      None),
     "map_frags":     _Cap("n_mini",  2,  True,  "raise", "frag_post",  "before"),
     "map_frag_seqs": _Cap("n_bases", 16, True,  "raise", "again",      "before"),  # again: the flip is part of the call
-    # align1: the room is for CIGAR words, not hits; a guess of one word per four read bases, the whole call again with the exact count
+    # _cigars: the room is for CIGAR words, not hits.  align1: a guess of one word per four read bases, the whole call again with the exact count
     "align1":        _Cap("n_bases", 4,  True,  "raise", "again",      None),
     "align1_inv":    _Cap("n_bases", 4,  True,  "raise", "again",      None),      # the same for the inversions' CIGAR words
+    "ksw_extd":      _Cap("n_span",  1,  False, "raise", None,         None),      # room for q_len + t_len words a problem: never short
 }
 
 
@@ -396,6 +397,28 @@ class Device:
             self._n_reads, self._total = n_reads, int(na.value)
         return off, regs[:int(off[-1])], None if rep is None else rep[:n_reads], int(na.value)
 
+    # -- the calls that return CIGARs: the same for their room, by their rows of _CAPS
+    def _cigars(self, method, cigar_cap, alloc, call, names, **size):
+        """alloc() -> the call's output arrays but the CIGARs, fresh ones, cigar_off last; call(*outputs, cigar pointer, cap) -> rc.
+        cigar_cap None: the row's guess, and where the row says so the call again with the exact count when it was short.  A cap that
+        stays short raises ChainDPError with the outputs attached under `names`.  Returns (*outputs, cigar uint32[cigar_off[-1]])."""
+        row = _CAPS[method]
+        cap = int(cigar_cap) if cigar_cap is not None else max(size[row.source] // row.divisor, REGS_CAP_FLOOR if row.floored else 1)
+        while True:
+            outs = alloc()
+            off, cigar = outs[-1], np.zeros(max(cap, 1), np.uint32)
+            rc = call(*outs, _ptr(cigar) if cap > 0 else None, max(cap, 0))
+            short = rc == ERR_CAPACITY and int(off[-1]) > cap >= 0
+            if not (short and cigar_cap is None and row.retry == "again"):
+                break
+            cap = int(off[-1])
+        if short:
+            err = ChainDPError(f"chaindp error {rc}: {self._lib.chaindp_last_error(self._ctx).decode()}")
+            err.__dict__.update(zip(names, outs))
+            raise err
+        self._check(rc)
+        return (*outs, cigar[:int(off[-1])])
+
     def map_batch(self, index, flag, max_occ, par, min_cnt, mini_off, mini, bid, qlen, hash_, regs_cap=None, gaps=None):
         """Minimizers in, hits out, everything in between resident (chaindp_map_batch): (regs_off int64[n_reads+1], regs REG_DTYPE[...],
         rep_len int32[n_reads], n_anchors)."""
@@ -547,22 +570,18 @@ class Device:
         if n and (int((q_beg + q_len).max()) > len(bases) or int((t_beg + t_len).max()) > len(bases)):
             raise ValueError("a problem reaches past the end of bases")
         a, b, q, e, q2, e2 = (int(v) for v in scoring)
-        cap = int(q_len.astype(np.int64).sum() + t_len.astype(np.int64).sum()) if cigar_cap is None else int(cigar_cap)
-        ez, off, cigar = np.zeros((n, 10), np.int32), np.zeros(n + 1, np.int64), np.zeros(max(cap, 1), np.uint32)
-        rc = self._lib.chaindp_ksw_extd(self._ctx, n, _ptr0(bases), _ptr(q_beg), _ptr(q_len), _ptr(t_beg), _ptr(t_len), a, b, q, e, q2, e2,
-                                        *[_ptr(v) for v in per], _ptr(ez), _ptr(off), _ptr(cigar) if cap > 0 else None, max(cap, 0))
-        if rc == ERR_CAPACITY and int(off[-1]) > cap >= 0:
-            err = ChainDPError(f"chaindp error {rc}: {self._lib.chaindp_last_error(self._ctx).decode()}")
-            err.ez, err.cigar_off = ez, off
-            raise err
-        self._check(rc)
-        return ez, off, cigar[:int(off[-1])]
+
+        def call(ez, off, cigar, cap):
+            return self._lib.chaindp_ksw_extd(self._ctx, n, _ptr0(bases), _ptr(q_beg), _ptr(q_len), _ptr(t_beg), _ptr(t_len), a, b, q, e, q2, e2,
+                                              *[_ptr(v) for v in per], _ptr(ez), _ptr(off), cigar, cap)
+        return self._cigars("ksw_extd", cigar_cap, lambda: (np.zeros((n, 10), np.int32), np.zeros(n + 1, np.int64)), call, ("ez", "cigar_off"),
+                            n_span=int(q_len.astype(np.int64).sum() + t_len.astype(np.int64).sum()))
 
     # -- base-level alignment of regions: mm_align1 around that DP (chaindp_align1)
     def align_set_targets(self, seq_off, seq):
         """The target sequences as characters (seq_off int64[n + 1], seq bytes / uint8), encoded on the device and kept resident until
         the next call or align_clear_targets()."""
-        seq_off, seq = _arr(seq_off, np.int64), np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else _arr(seq, np.uint8)
+        seq, seq_off = self._seqs(seq, seq_off)
         if len(seq_off) < 1 or int(seq_off[-1]) != len(seq):
             raise ValueError("seq_off must end at the number of bases")
         self._check(self._lib.chaindp_align_set_targets(self._ctx, len(seq_off) - 1, _ptr(seq_off), _ptr0(seq)))
@@ -577,30 +596,20 @@ class Device:
         their MM_SEED_IGNORE marks, the updated regions, what was split off (cnt 0 where nothing was; regs2 given: its other fields stay).
         cigar_cap None: a guess, and the call again with the exact count where it was short (the _CAPS row); with a cap of the caller's
         that is too small the call raises ChainDPError and err.a / .regs / .regs2 / .extra / .cigar_off hold what the C call filled in."""
-        seq_off, a_off, regs_off = _arr(seq_off, np.int64), _arr(a_off, np.int64), _arr(regs_off, np.int64)
-        seq = np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else _arr(seq, np.uint8)
+        (seq, seq_off), a_off, regs_off = self._seqs(seq, seq_off), _arr(a_off, np.int64), _arr(regs_off, np.int64)
         a_in, regs_in = _arr(a, np.uint64).reshape(-1, 2), _arr(regs, REG_DTYPE)
         n_reads, n_regs = len(seq_off) - 1, len(regs_in)
         if len(a_off) != n_reads + 1 or len(regs_off) != n_reads + 1 or int(a_off[-1]) != len(a_in) or int(regs_off[-1]) != n_regs or int(seq_off[-1]) != len(seq):
             raise ValueError("seq_off, a_off and regs_off need one entry per read and one more, and must end at the sizes of seq, a and regs")
-        row = _CAPS["align1"]
-        cap = int(cigar_cap) if cigar_cap is not None else max(len(seq) // row.divisor, REGS_CAP_FLOOR if row.floored else 1)
-        while True:
-            a_out, regs_out = a_in.copy(), regs_in.copy()
+
+        def alloc():
             r2 = np.zeros(n_regs, REG_DTYPE) if regs2 is None else _arr(regs2, REG_DTYPE).copy()
-            extra, off, cigar = np.zeros(n_regs, ALIGN_EXTRA_DTYPE), np.zeros(n_regs + 1, np.int64), np.zeros(max(cap, 1), np.uint32)
-            rc = self._lib.chaindp_align1(self._ctx, C.byref(opt), n_reads, _ptr(seq_off), _ptr0(seq), _ptr(a_off), _ptr0(a_out), _ptr(regs_off),
-                                          _ptr0(regs_out), _ptr0(r2), _ptr0(extra), _ptr(off), _ptr(cigar) if cap > 0 else None, max(cap, 0))
-            short = rc == ERR_CAPACITY and int(off[-1]) > cap >= 0
-            if short and cigar_cap is None and row.retry == "again":
-                cap = int(off[-1])
-                continue
-            if short:
-                err = ChainDPError(f"chaindp error {rc}: {self._lib.chaindp_last_error(self._ctx).decode()}")
-                err.a, err.regs, err.regs2, err.extra, err.cigar_off = a_out, regs_out, r2, extra, off
-                raise err
-            self._check(rc)
-            return a_out, regs_out, r2, extra, off, cigar[:int(off[-1])]
+            return a_in.copy(), regs_in.copy(), r2, np.zeros(n_regs, ALIGN_EXTRA_DTYPE), np.zeros(n_regs + 1, np.int64)
+
+        def call(a_out, regs_out, r2, extra, off, cigar, cap):
+            return self._lib.chaindp_align1(self._ctx, C.byref(opt), n_reads, _ptr(seq_off), _ptr0(seq), _ptr(a_off), _ptr0(a_out), _ptr(regs_off),
+                                            _ptr0(regs_out), _ptr0(r2), _ptr0(extra), _ptr(off), cigar, cap)
+        return self._cigars("align1", cigar_cap, alloc, call, ("a", "regs", "regs2", "extra", "cigar_off"), n_bases=len(seq))
 
     def align1_inv(self, opt, seq_off, seq, regs_off, regs, cigar_cap=None):
         """mm_align1_inv for every pair of neighbouring regions of every read (chaindp_align1_inv), after all align1 rounds: regs REG_DTYPE in
@@ -609,29 +618,19 @@ class Device:
         cigar_off int64[n_regions + 1], cigar uint32[...]); made: 0 no test, 1 made, 2 below min_dp_max, 3 not tested because the pair before
         it was made, 4 no CIGAR.  cigar_cap as align1's; a cap of the caller's that is too small raises ChainDPError with err.made /
         .r_inv / .extra / .cigar_off holding what the C call filled in."""
-        seq_off, regs_off = _arr(seq_off, np.int64), _arr(regs_off, np.int64)
-        seq = np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else _arr(seq, np.uint8)
+        (seq, seq_off), regs_off = self._seqs(seq, seq_off), _arr(regs_off, np.int64)
         regs_in = _arr(regs, REG_DTYPE)
         n_reads, n_regs = len(seq_off) - 1, len(regs_in)
         if len(regs_off) != n_reads + 1 or int(regs_off[-1]) != n_regs or int(seq_off[-1]) != len(seq):
             raise ValueError("seq_off and regs_off need one entry per read and one more, and must end at the sizes of seq and regs")
-        row = _CAPS["align1_inv"]
-        cap = int(cigar_cap) if cigar_cap is not None else max(len(seq) // row.divisor, REGS_CAP_FLOOR if row.floored else 1)
-        while True:
-            made, r_inv, extra = np.zeros(n_regs, np.int32), np.zeros(n_regs, REG_DTYPE), np.zeros(n_regs, ALIGN_EXTRA_DTYPE)
-            off, cigar = np.zeros(n_regs + 1, np.int64), np.zeros(max(cap, 1), np.uint32)
-            rc = self._lib.chaindp_align1_inv(self._ctx, C.byref(opt), n_reads, _ptr(seq_off), _ptr0(seq), _ptr(regs_off), _ptr0(regs_in), _ptr0(made),
-                                              _ptr0(r_inv), _ptr0(extra), _ptr(off), _ptr(cigar) if cap > 0 else None, max(cap, 0))
-            short = rc == ERR_CAPACITY and int(off[-1]) > cap >= 0
-            if short and cigar_cap is None and row.retry == "again":
-                cap = int(off[-1])
-                continue
-            if short:
-                err = ChainDPError(f"chaindp error {rc}: {self._lib.chaindp_last_error(self._ctx).decode()}")
-                err.made, err.r_inv, err.extra, err.cigar_off = made, r_inv, extra, off
-                raise err
-            self._check(rc)
-            return made, r_inv, extra, off, cigar[:int(off[-1])]
+
+        def alloc():
+            return np.zeros(n_regs, np.int32), np.zeros(n_regs, REG_DTYPE), np.zeros(n_regs, ALIGN_EXTRA_DTYPE), np.zeros(n_regs + 1, np.int64)
+
+        def call(made, r_inv, extra, off, cigar, cap):
+            return self._lib.chaindp_align1_inv(self._ctx, C.byref(opt), n_reads, _ptr(seq_off), _ptr0(seq), _ptr(regs_off), _ptr0(regs_in), _ptr0(made),
+                                                _ptr0(r_inv), _ptr0(extra), _ptr(off), cigar, cap)
+        return self._cigars("align1_inv", cigar_cap, alloc, call, ("made", "r_inv", "extra", "cigar_off"), n_bases=len(seq))
 
     def align_inv_ll(self, n):
         """score, qe, te of ksw_ll_i16 for the n candidate pairs of the last align1_inv, on the reversed stretches (test hook): int32[n, 3]."""

@@ -1,6 +1,7 @@
 // chaindp_abi_align.cpp -- the region alignment stage of the host ABI (include/chaindp_align.h): mm_align1 for a batch of regions.
-// The checks and the layout of the problems are chaindp_align_plan.h's, the kernels chaindp_align.hip's, the DP chaindp_ksw_extd's own
-// (ksw_plan_route, ksw_reserve, ksw_dispatch); this file owns the buffers, the copies and the order of the launches:
+// The checks and the layout of the problems are chaindp_align_plan.h's, the kernels chaindp_align.hip's, the DP, the stage events and
+// the CIGARs out the alignment stages' scaffold (chaindp_ctx.h: ksw_plan_route, ksw_reserve, ksw_dispatch, ksw_view, StageEvents,
+// cigar_pack_out); this file owns the stage's own buffers, the copies and the order of the launches:
 //   plan -> (lengths down, offsets up) -> gather -> DP -> zdrop -> (codes down) -> DP of the second pass -> stitch -> extra -> (counts down) -> pack
 #include "chaindp_ctx.h"
 #include "../../include/chaindp_align.h"
@@ -67,18 +68,6 @@ extern "C" int chaindp_align_debug_ms(chaindp_ctx_t *ctx, double ms[5])
 	return CHAINDP_OK;
 }
 
-namespace {
-struct Carve {                       // consecutive 16-byte aligned pieces of one buffer
-	size_t at = 0;
-	size_t take(size_t bytes) { const size_t o = at; at += (bytes + 15) / 16 * 16; return o; }
-};
-struct Events {                      // while profiling is on: an event at every boundary between the stages
-	std::vector<hipEvent_t> e;
-	std::vector<int> stage;          // the stage that ends at e[k] (-1: host time, not counted)
-	~Events() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
-};
-}
-
 extern "C" int chaindp_align1(chaindp_ctx_t *ctx, const chaindp_align_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seq,
                               const int64_t *a_off, chaindp_anchor_t *a, const int64_t *regs_off, chaindp_reg_t *regs, chaindp_reg_t *regs2,
                               chaindp_align_extra_t *extra, int64_t *cigar_off, uint32_t *cigar, int64_t cigar_cap)
@@ -139,17 +128,10 @@ extern "C" int chaindp_align1(chaindp_ctx_t *ctx, const chaindp_align_opt_t *opt
 	HIP_TRY(ctx, up(o_regs, regs, (size_t)G * 80));
 	HIP_TRY(ctx, up(o_regs2, regs2, (size_t)G * 80));
 	HIP_TRY(ctx, up(o_seq, seq, (size_t)ap.n_bases));
-	Events ev;
-	auto mark = [&](int stage) -> hipError_t {
-		if (!ctx->prof) return hipSuccess;
-		hipEvent_t e;
-		if (hipError_t err = hipEventCreate(&e)) return err;
-		ev.e.push_back(e); ev.stage.push_back(stage);
-		return hipEventRecord(e, st);
-	};
-	HIP_TRY(ctx, mark(-1));
+	StageEvents ev(ctx);
+	HIP_TRY(ctx, ev.mark(-1));
 	HIP_TRY(ctx, launch_align_plan(st, o, d));
-	HIP_TRY(ctx, mark(0));
+	HIP_TRY(ctx, ev.mark(0));
 	std::vector<AlignReg> areg((size_t)G);
 	std::vector<KswProb> slots(S);
 	HIP_TRY(ctx, hipMemcpyAsync(areg.data(), d.areg, (size_t)G * sizeof(AlignReg), hipMemcpyDeviceToHost, st));
@@ -181,20 +163,20 @@ extern "C" int chaindp_align1(chaindp_ctx_t *ctx, const chaindp_align_opt_t *opt
 	if (P) {
 		HIP_TRY(ctx, hipMemcpyAsync(d_pc + o_prob, p1.prob.data(), P * sizeof(KswProb), hipMemcpyHostToDevice, st));
 		HIP_TRY(ctx, hipMemcpyAsync(d_pc + o_src, src_slot.data(), P * 4, hipMemcpyHostToDevice, st));
-		HIP_TRY(ctx, mark(-1));
+		HIP_TRY(ctx, ev.mark(-1));
 		HIP_TRY(ctx, launch_align_gather(st, d, (uint8_t*)ctx->ksw_bases.p));
-		HIP_TRY(ctx, mark(0));
-		if ((rc = ksw_dispatch(ctx, p1, nullptr, nullptr))) return rc;
-		HIP_TRY(ctx, mark(1));
-		const int32_t *d_ez = (const int32_t*)((const int64_t*)ctx->ksw_ez.p + 2 + P + 1);
+		HIP_TRY(ctx, ev.mark(0));
+		if ((rc = ksw_dispatch(ctx, p1, nullptr))) return rc;
+		HIP_TRY(ctx, ev.mark(1));
+		const KswView v1 = ksw_view(ctx, P);
 		int max_t = 0;
 		for (size_t c = 0; c < P; ++c) max_t = std::max(max_t, p1.prob[c].tlen);
 		const int lds_t = std::max(std::min(max_t, o.max_gap - 1), 0) + 1;
-		HIP_TRY(ctx, launch_align_zdrop(st, o, d, (const uint8_t*)ctx->ksw_bases.p, d_ez, (const uint32_t*)ctx->ksw_cig.p, lds_t));
-		HIP_TRY(ctx, mark(2));
+		HIP_TRY(ctx, launch_align_zdrop(st, o, d, (const uint8_t*)ctx->ksw_bases.p, v1.ez, v1.cig, lds_t));
+		HIP_TRY(ctx, ev.mark(2));
 		// the first pass's answers out of the DP's buffers: the second pass writes there
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->al_ez1.p, d_ez, P * KSW_EZ_WORDS * 4, hipMemcpyDeviceToDevice, st));
-		if (p1.cig_words) HIP_TRY(ctx, hipMemcpyAsync(ctx->al_cig1.p, ctx->ksw_cig.p, (size_t)p1.cig_words * 4, hipMemcpyDeviceToDevice, st));
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->al_ez1.p, v1.ez, P * KSW_EZ_WORDS * 4, hipMemcpyDeviceToDevice, st));
+		if (p1.cig_words) HIP_TRY(ctx, hipMemcpyAsync(ctx->al_cig1.p, v1.cig, (size_t)p1.cig_words * 4, hipMemcpyDeviceToDevice, st));
 		std::vector<int32_t> code(P);
 		HIP_TRY(ctx, hipMemcpyAsync(code.data(), d.code, P * 4, hipMemcpyDeviceToHost, st));
 		HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -211,46 +193,27 @@ extern "C" int chaindp_align1(chaindp_ctx_t *ctx, const chaindp_align_opt_t *opt
 		if (!p2.prob.empty()) {
 			ksw_plan_route(p2, ctx->dp.cus, ctx->ksw_grid_cap);
 			if ((rc = ksw_reserve(ctx, p2, n_bases, WHO))) return rc;
-			HIP_TRY(ctx, mark(-1));
-			if ((rc = ksw_dispatch(ctx, p2, nullptr, nullptr))) return rc;
-			HIP_TRY(ctx, mark(1));
+			HIP_TRY(ctx, ev.mark(-1));
+			if ((rc = ksw_dispatch(ctx, p2, nullptr))) return rc;
+			HIP_TRY(ctx, ev.mark(1));
 		}
 	}
-	const size_t P2 = p2.prob.size();
-	HIP_TRY(ctx, mark(-1));
-	HIP_TRY(ctx, launch_align_stitch(st, o, d, p1.cig_words, (const KswProb*)ctx->ksw_prob.p, (const int32_t*)((const int64_t*)ctx->ksw_ez.p + 2 + P2 + 1),
-	                                 (const uint32_t*)ctx->ksw_cig.p));
-	HIP_TRY(ctx, mark(3));
+	const KswView v2 = ksw_view(ctx, p2.prob.size());
+	HIP_TRY(ctx, ev.mark(-1));
+	HIP_TRY(ctx, launch_align_stitch(st, o, d, p1.cig_words, v2.prob, v2.ez, v2.cig));
+	HIP_TRY(ctx, ev.mark(3));
 	HIP_TRY(ctx, launch_align_extra(st, o, d));
-	HIP_TRY(ctx, mark(4));
+	HIP_TRY(ctx, ev.mark(4));
 	HIP_TRY(ctx, hipMemcpyAsync(extra, d.extra, (size_t)G * 20, hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipMemcpyAsync(regs, d.regs, (size_t)G * 80, hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipMemcpyAsync(regs2, d.regs2, (size_t)G * 80, hipMemcpyDeviceToHost, st));
 	if (ap.n_anchors) HIP_TRY(ctx, hipMemcpyAsync(a, d.a, (size_t)ap.n_anchors * 16, hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipStreamSynchronize(st));
-	for (int64_t g = 0; g < G; ++g) cigar_off[g + 1] = cigar_off[g] + extra[g].n_cigar;
-	const int64_t total = cigar_off[G];
-	int ret = CHAINDP_OK;
-	if (total > cigar_cap) {
-		ctx->err = "chaindp_align1: " + std::to_string((long long)total) + " CIGAR words, room for " + std::to_string((long long)cigar_cap);
-		ret = CHAINDP_ERR_CAPACITY;
-	} else if (total > 0) {
-		if ((rc = ksw_grow(ctx, ctx->al_out, (size_t)total * 4 + 16, "CIGARs", WHO))) return rc;
-		HIP_TRY(ctx, hipMemcpyAsync(d_coff, cigar_off, (size_t)(G + 1) * 8, hipMemcpyHostToDevice, st));
-		HIP_TRY(ctx, mark(-1));
-		HIP_TRY(ctx, launch_align_pack(st, d, d_coff, (uint32_t*)ctx->al_out.p));
-		HIP_TRY(ctx, mark(4));
-		HIP_TRY(ctx, hipMemcpyAsync(cigar, ctx->al_out.p, (size_t)total * 4, hipMemcpyDeviceToHost, st));
-		HIP_TRY(ctx, hipStreamSynchronize(st));
-	}
-	if (!ev.e.empty()) {
-		for (double &m : ctx->al_ms) m = 0;
-		for (size_t k = 1; k < ev.e.size(); ++k) {
-			if (ev.stage[k] < 0) continue;
-			float ms = 0;
-			HIP_TRY(ctx, hipEventElapsedTime(&ms, ev.e[k - 1], ev.e[k]));
-			ctx->al_ms[ev.stage[k]] += ms;
-		}
-	}
+	const int64_t total = cigar_prefix((const int32_t*)extra, 5, 4, G, cigar_off);
+	const int ret = cigar_pack_out(ctx, WHO, cigar_off, G, total, cigar, cigar_cap, d_coff, [&](uint32_t *out) {
+		hipError_t e;
+		return (e = ev.mark(-1)) || (e = launch_align_pack(st, d, d_coff, out)) ? e : ev.mark(4);
+	});
+	if (ret != CHAINDP_ERR_HIP && (rc = ev.fold(ctx->al_ms, 5))) return rc;
 	return ret;
 }

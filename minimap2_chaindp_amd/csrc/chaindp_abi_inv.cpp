@@ -1,6 +1,7 @@
 // chaindp_abi_inv.cpp -- the inversion stage of the host ABI (include/chaindp_align_inv.h): mm_align1_inv for every pair of neighbouring regions.
-// The checks, the early returns and the extension problems are chaindp_inv_plan.h's, the kernels inv/chaindp_inv.hip's, the DP
-// chaindp_ksw_extd's own (ksw_plan_route, ksw_reserve, ksw_dispatch); this file owns the buffers, the copies and the order of the launches:
+// The checks, the early returns and the extension problems are chaindp_inv_plan.h's, the kernels inv/chaindp_inv.hip's, the DP, the
+// stage events and the CIGARs out the alignment stages' scaffold (chaindp_ctx.h: ksw_plan_route, ksw_reserve, ksw_dispatch, ksw_view,
+// StageEvents, cigar_pack_out); this file owns the stage's own buffers, the copies and the order of the launches:
 //   candidates up -> local score -> (scores down, survivors and problems up) -> gather -> DP -> finish -> skip rule -> (counts down) -> pack
 #include "chaindp_ctx.h"
 #include "../../include/chaindp_align_inv.h"
@@ -8,8 +9,6 @@
 
 using namespace chaindp;
 
-static_assert(sizeof(chaindp_align_opt_t) == sizeof(AlignOpt), "chaindp_align_opt_t is AlignOpt");
-static_assert(sizeof(chaindp_reg_t) == AL_REG_WORDS * 4, "chaindp_reg_t in words");
 static const char *const WHO = "chaindp_align1_inv";
 
 extern "C" int chaindp_align_inv_debug_check(const chaindp_align_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const int64_t *regs_off,
@@ -37,18 +36,6 @@ extern "C" int chaindp_align_inv_debug_ms(chaindp_ctx_t *ctx, double ms[4])
 	if (!ctx || !ms) return CHAINDP_ERR_ARG;
 	for (int k = 0; k < 4; ++k) ms[k] = ctx->inv_ms[k];
 	return CHAINDP_OK;
-}
-
-namespace {
-struct Carve {                       // consecutive 16-byte aligned pieces of one buffer
-	size_t at = 0;
-	size_t take(size_t bytes) { const size_t o = at; at += (bytes + 15) / 16 * 16; return o; }
-};
-struct Events {                      // while profiling is on: an event at every boundary between the stages
-	std::vector<hipEvent_t> e;
-	std::vector<int> stage;          // the stage that ends at e[k] (-1: host time, not counted)
-	~Events() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
-};
 }
 
 extern "C" int chaindp_align1_inv(chaindp_ctx_t *ctx, const chaindp_align_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seq,
@@ -107,17 +94,10 @@ extern "C" int chaindp_align1_inv(chaindp_ctx_t *ctx, const chaindp_align_opt_t 
 	HIP_TRY(ctx, up(d_in, o_slot_cand, ip.slot_cand.data(), (size_t)G * 4));
 	HIP_TRY(ctx, up(d_in, o_seq, seq, (size_t)ip.n_bases));
 	HIP_TRY(ctx, hipMemsetAsync(d_rs, 0, o_coff, st));
-	Events ev;
-	auto mark = [&](int stage) -> hipError_t {
-		if (!ctx->prof) return hipSuccess;
-		hipEvent_t e;
-		if (hipError_t err = hipEventCreate(&e)) return err;
-		ev.e.push_back(e); ev.stage.push_back(stage);
-		return hipEventRecord(e, st);
-	};
-	HIP_TRY(ctx, mark(-1));
+	StageEvents ev(ctx);
+	HIP_TRY(ctx, ev.mark(-1));
 	HIP_TRY(ctx, launch_inv_ll(st, o, d, (int)inv_ll_rows(ip.max_ql), d_out3));
-	HIP_TRY(ctx, mark(0));
+	HIP_TRY(ctx, ev.mark(0));
 	std::vector<int32_t> out3(C * 3);
 	HIP_TRY(ctx, hipMemcpyAsync(out3.data(), d_out3, C * 12, hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -131,44 +111,27 @@ extern "C" int chaindp_align1_inv(chaindp_ctx_t *ctx, const chaindp_align_opt_t 
 	if (S) {
 		ksw_plan_route(kp, ctx->dp.cus, ctx->ksw_grid_cap);
 		if ((rc = ksw_reserve(ctx, kp, n_bases, WHO))) return rc;
+		const KswView v = ksw_view(ctx, S);
 		HIP_TRY(ctx, up(d_ll, o_surv, surv.data(), S * sizeof(InvSurv)));
 		HIP_TRY(ctx, up(d_ll, o_prob, kp.prob.data(), S * sizeof(KswProb)));
-		HIP_TRY(ctx, mark(-1));
+		HIP_TRY(ctx, ev.mark(-1));
 		HIP_TRY(ctx, launch_inv_gather(st, d, (uint8_t*)ctx->ksw_bases.p));
-		if ((rc = ksw_dispatch(ctx, kp, nullptr, nullptr))) return rc;
-		HIP_TRY(ctx, mark(1));
-		HIP_TRY(ctx, launch_inv_finish(st, o, d, (const int32_t*)((const int64_t*)ctx->ksw_ez.p + 2 + S + 1), (uint32_t*)ctx->ksw_cig.p));
-	} else HIP_TRY(ctx, mark(-1));
+		if ((rc = ksw_dispatch(ctx, kp, nullptr))) return rc;
+		HIP_TRY(ctx, ev.mark(1));
+		HIP_TRY(ctx, launch_inv_finish(st, o, d, v.ez, v.cig));
+	} else HIP_TRY(ctx, ev.mark(-1));
 	HIP_TRY(ctx, launch_inv_skip(st, d));
-	HIP_TRY(ctx, mark(2));
+	HIP_TRY(ctx, ev.mark(2));
 	HIP_TRY(ctx, hipMemcpyAsync(made, d.made, (size_t)G * 4, hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipMemcpyAsync(r_inv, d.r_inv, (size_t)G * 80, hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipMemcpyAsync(extra, d.extra, (size_t)G * 20, hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipStreamSynchronize(st));
 	if (S) ctx->ksw_n = (int64_t)S;                      // chaindp_ksw_debug_route: the extensions' routes
-	for (int64_t g = 0; g < G; ++g) cigar_off[g + 1] = cigar_off[g] + extra[g].n_cigar;
-	const int64_t total = cigar_off[G];
-	int ret = CHAINDP_OK;
-	if (total > cigar_cap) {
-		ctx->err = "chaindp_align1_inv: " + std::to_string((long long)total) + " CIGAR words, room for " + std::to_string((long long)cigar_cap);
-		ret = CHAINDP_ERR_CAPACITY;
-	} else if (total > 0) {
-		if ((rc = ksw_grow(ctx, ctx->inv_out, (size_t)total * 4 + 16, "CIGARs", WHO))) return rc;
-		HIP_TRY(ctx, hipMemcpyAsync(d_coff, cigar_off, (size_t)(G + 1) * 8, hipMemcpyHostToDevice, st));
-		HIP_TRY(ctx, mark(-1));
-		HIP_TRY(ctx, launch_inv_pack(st, d, d_coff, (const uint32_t*)ctx->ksw_cig.p, (uint32_t*)ctx->inv_out.p));
-		HIP_TRY(ctx, mark(3));
-		HIP_TRY(ctx, hipMemcpyAsync(cigar, ctx->inv_out.p, (size_t)total * 4, hipMemcpyDeviceToHost, st));
-		HIP_TRY(ctx, hipStreamSynchronize(st));
-	}
-	if (!ev.e.empty()) {
-		for (double &m : ctx->inv_ms) m = 0;
-		for (size_t k = 1; k < ev.e.size(); ++k) {
-			if (ev.stage[k] < 0) continue;
-			float ms = 0;
-			HIP_TRY(ctx, hipEventElapsedTime(&ms, ev.e[k - 1], ev.e[k]));
-			ctx->inv_ms[ev.stage[k]] += ms;
-		}
-	}
+	const int64_t total = cigar_prefix((const int32_t*)extra, 5, 4, G, cigar_off);
+	const int ret = cigar_pack_out(ctx, WHO, cigar_off, G, total, cigar, cigar_cap, d_coff, [&](uint32_t *out) {
+		hipError_t e;
+		return (e = ev.mark(-1)) || (e = launch_inv_pack(st, d, d_coff, ksw_view(ctx, S).cig, out)) ? e : ev.mark(3);
+	});
+	if (ret != CHAINDP_ERR_HIP && (rc = ev.fold(ctx->inv_ms, 4))) return rc;
 	return ret;
 }

@@ -1,5 +1,6 @@
-// chaindp_abi_ksw.cpp -- the alignment stage of the host ABI (include/chaindp_ksw.h): ksw_extd2_sse for a batch of problems.
-// The plan (checks, records, order, sizes) is chaindp_ksw_plan.h's; this file owns the buffers, the copies and the two launches.
+// chaindp_abi_ksw.cpp -- the alignment stage of the host ABI (include/chaindp_ksw.h): ksw_extd2_sse for a batch of problems, and the
+// host scaffold it shares with chaindp_align1 and chaindp_align1_inv (declared in chaindp_ctx.h): the DP's buffers and their view, the
+// two launches, the stage events, the CIGARs out.  The plan (checks, records, order, sizes, the buffers' layout) is chaindp_ksw_plan.h's.
 #include "chaindp_ctx.h"
 #include <string.h>
 
@@ -18,11 +19,11 @@ int chaindp::ksw_grow(chaindp_ctx *ctx, DevGrow &g, size_t need, const char *wha
 // every buffer a planned batch needs (the stream is idle: a buffer that grows is freed)
 int chaindp::ksw_reserve(chaindp_ctx *ctx, const KswPlan &pl, int64_t n_bases, const char *who)
 {
-	const size_t N = pl.prob.size();
+	const KswLayout lay(pl.prob.size());
 	int rc;
 	if ((rc = ksw_grow(ctx, ctx->ksw_bases, (size_t)n_bases + 16, "sequences", who))) return rc;
-	if ((rc = ksw_grow(ctx, ctx->ksw_prob, N * sizeof(KswProb) + N * sizeof(int32_t) + 16, "problem records", who))) return rc;
-	if ((rc = ksw_grow(ctx, ctx->ksw_ez, N * KSW_EZ_WORDS * sizeof(int32_t) + (N + 1) * sizeof(int64_t) + 32, "results", who))) return rc;
+	if ((rc = ksw_grow(ctx, ctx->ksw_prob, lay.prob_bytes, "problem records", who))) return rc;
+	if ((rc = ksw_grow(ctx, ctx->ksw_ez, lay.ez_bytes, "results", who))) return rc;
 	if ((rc = ksw_grow(ctx, ctx->ksw_state, (size_t)pl.grid[0] * pl.state_stride + 16, "DP state", who))) return rc;
 	if ((rc = ksw_grow(ctx, ctx->ksw_path, (size_t)pl.grid[0] * pl.path_stride[0] + (size_t)pl.grid[1] * pl.path_stride[1] + 16, "path matrices", who))) return rc;
 	if ((rc = ksw_grow(ctx, ctx->ksw_cig, (size_t)pl.cig_words * sizeof(uint32_t) + 16, "CIGAR staging", who))) return rc;
@@ -34,27 +35,66 @@ int chaindp::ksw_reserve(chaindp_ctx *ctx, const KswPlan &pl, int64_t n_bases, c
 	return CHAINDP_OK;
 }
 
-// the records and their order up, the two launches; the bases are on the device already.  ev0 / ev1 (or null): recorded around the launches
-int chaindp::ksw_dispatch(chaindp_ctx *ctx, const KswPlan &pl, hipEvent_t ev0, hipEvent_t ev1)
+KswView chaindp::ksw_view(const chaindp_ctx *ctx, size_t N)
+{
+	const KswLayout lay(N);
+	char *prob = (char*)ctx->ksw_prob.p, *ez = (char*)ctx->ksw_ez.p;
+	return KswView{(KswProb*)prob, (int32_t*)(prob + lay.order), (unsigned int*)ez, (int64_t*)(ez + lay.off), (int32_t*)(ez + lay.ez), (uint32_t*)ctx->ksw_cig.p};
+}
+
+StageEvents::~StageEvents() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
+
+hipError_t StageEvents::mark(int stage_)
+{
+	if (!ctx->prof) return hipSuccess;
+	hipEvent_t x;
+	if (hipError_t err = hipEventCreate(&x)) return err;
+	e.push_back(x); stage.push_back(stage_);
+	return hipEventRecord(x, ctx->stream);
+}
+
+int StageEvents::fold(double *ms, int n)
+{
+	if (e.empty()) return CHAINDP_OK;
+	for (int k = 0; k < n; ++k) ms[k] = 0;
+	for (size_t k = 1; k < e.size(); ++k) {
+		if (stage[k] < 0) continue;
+		float t = 0;
+		HIP_TRY(ctx, hipEventElapsedTime(&t, e[k - 1], e[k]));
+		ms[stage[k]] += t;
+	}
+	return CHAINDP_OK;
+}
+
+int chaindp::ksw_dispatch(chaindp_ctx *ctx, const KswPlan &pl, StageEvents *ev)
 {
 	const size_t N = pl.prob.size();
 	hipStream_t st = ctx->stream;
-	// ksw_prob: the records, then the order; ksw_ez: the two launches' counters (8 bytes each), the CSR offsets, the result words
-	KswProb *d_prob = (KswProb*)ctx->ksw_prob.p;
-	int32_t *d_order = (int32_t*)(d_prob + N);
-	unsigned int *d_counter = (unsigned int*)ctx->ksw_ez.p;
-	int32_t *d_ez = (int32_t*)((int64_t*)ctx->ksw_ez.p + 2 + N + 1);
-	HIP_TRY(ctx, hipMemcpyAsync(d_prob, pl.prob.data(), N * sizeof(KswProb), hipMemcpyHostToDevice, st));
-	HIP_TRY(ctx, hipMemcpyAsync(d_order, pl.order.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, st));
-	if (ev0) HIP_TRY(ctx, hipEventRecord(ev0, st));
+	const KswView v = ksw_view(ctx, N);
+	HIP_TRY(ctx, hipMemcpyAsync(v.prob, pl.prob.data(), N * sizeof(KswProb), hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, hipMemcpyAsync(v.order, pl.order.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, st));
+	if (ev) HIP_TRY(ctx, ev->mark(-1));
 	// the wide problems first: theirs are the long workgroups, the one-wave ones fill in behind them
-	HIP_TRY(ctx, launch_ksw_extd(st, KSW_WIDE_WAVES, pl.grid[1], pl.lds_bytes[1], pl.count[1], d_prob, d_order + pl.count[0], (const uint8_t*)ctx->ksw_bases.p,
-	                             pl.sc, nullptr, 0, (uint8_t*)ctx->ksw_path.p + (size_t)pl.grid[0] * pl.path_stride[0], pl.path_stride[1], d_ez,
-	                             (uint32_t*)ctx->ksw_cig.p, d_counter + 2));
-	HIP_TRY(ctx, launch_ksw_extd(st, 1, pl.grid[0], pl.lds_bytes[0], pl.count[0], d_prob, d_order, (const uint8_t*)ctx->ksw_bases.p, pl.sc,
-	                             (uint8_t*)ctx->ksw_state.p, pl.state_stride, (uint8_t*)ctx->ksw_path.p, pl.path_stride[0], d_ez, (uint32_t*)ctx->ksw_cig.p,
-	                             d_counter));
-	if (ev1) HIP_TRY(ctx, hipEventRecord(ev1, st));
+	HIP_TRY(ctx, launch_ksw_extd(st, KSW_WIDE_WAVES, pl.grid[1], pl.lds_bytes[1], pl.count[1], v.prob, v.order + pl.count[0], (const uint8_t*)ctx->ksw_bases.p,
+	                             pl.sc, nullptr, 0, (uint8_t*)ctx->ksw_path.p + (size_t)pl.grid[0] * pl.path_stride[0], pl.path_stride[1], v.ez,
+	                             v.cig, v.counter + 2));
+	HIP_TRY(ctx, launch_ksw_extd(st, 1, pl.grid[0], pl.lds_bytes[0], pl.count[0], v.prob, v.order, (const uint8_t*)ctx->ksw_bases.p, pl.sc,
+	                             (uint8_t*)ctx->ksw_state.p, pl.state_stride, (uint8_t*)ctx->ksw_path.p, pl.path_stride[0], v.ez, v.cig, v.counter));
+	if (ev) HIP_TRY(ctx, ev->mark(0));
+	return CHAINDP_OK;
+}
+
+int chaindp::cigar_pack_out(chaindp_ctx *ctx, const char *who, const int64_t *cigar_off, int64_t n, int64_t total, uint32_t *cigar, int64_t cigar_cap,
+                            int64_t *d_off, const std::function<hipError_t(uint32_t *out)> &launch)
+{
+	if (!cigar_room(who, total, cigar_cap, ctx->err)) return CHAINDP_ERR_CAPACITY;
+	if (total == 0) return CHAINDP_OK;
+	hipStream_t st = ctx->stream;
+	if (int rc = ksw_grow(ctx, ctx->cigar_out, (size_t)total * sizeof(uint32_t) + 16, "CIGARs", who)) return rc;
+	HIP_TRY(ctx, hipMemcpyAsync(d_off, cigar_off, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, launch((uint32_t*)ctx->cigar_out.p));
+	HIP_TRY(ctx, hipMemcpyAsync(cigar, ctx->cigar_out.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+	HIP_TRY(ctx, hipStreamSynchronize(st));
 	return CHAINDP_OK;
 }
 
@@ -79,45 +119,20 @@ extern "C" int chaindp_ksw_extd(chaindp_ctx_t *ctx, int64_t n, const uint8_t *ba
 	int rc;
 	if ((rc = ksw_reserve(ctx, pl, pl.n_bases, "chaindp_ksw_extd"))) return rc;
 	hipStream_t st = ctx->stream;
-	KswProb *d_prob = (KswProb*)ctx->ksw_prob.p;
-	int64_t *d_off = (int64_t*)ctx->ksw_ez.p + 2;
-	int32_t *d_ez = (int32_t*)(d_off + N + 1);
+	const KswView v = ksw_view(ctx, N);
 	if (pl.n_bases) HIP_TRY(ctx, hipMemcpyAsync(ctx->ksw_bases.p, bases, (size_t)pl.n_bases, hipMemcpyHostToDevice, st));
-	struct Events {                                       // while profiling is on: the DP kernels' own time, apart from the copies around them
-		hipEvent_t e[2] = {nullptr, nullptr};
-		~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-		hipEvent_t operator[](int k) const { return e[k]; }
-	} ev;
-	if (ctx->prof) {
-		HIP_TRY(ctx, hipEventCreate(&ev.e[0]));
-		HIP_TRY(ctx, hipEventCreate(&ev.e[1]));
-	}
-	if ((rc = ksw_dispatch(ctx, pl, ev[0], ev[1]))) return rc;
+	StageEvents ev(ctx);                                 // the DP kernels' own time, apart from the copies around them
+	if ((rc = ksw_dispatch(ctx, pl, &ev))) return rc;
 	std::vector<int32_t> ez(N * KSW_EZ_WORDS);
-	HIP_TRY(ctx, hipMemcpyAsync(ez.data(), d_ez, ez.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+	HIP_TRY(ctx, hipMemcpyAsync(ez.data(), v.ez, ez.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipStreamSynchronize(st));
-	if (ev[0]) {
-		float ms = 0;
-		HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
-		ctx->ksw_ms = ms;
-	}
+	if ((rc = ev.fold(&ctx->ksw_ms, 1))) return rc;
 	ctx->ksw_n = n;
-	for (size_t i = 0; i < N; ++i) {
-		memcpy(ez_out + i * 10, ez.data() + i * KSW_EZ_WORDS, 10 * sizeof(int32_t));
-		cigar_off[i + 1] = cigar_off[i] + ez[i * KSW_EZ_WORDS + 10];
-	}
-	const int64_t total = cigar_off[N];
-	if (total > cigar_cap) {
-		ctx->err = "chaindp_ksw_extd: " + std::to_string((long long)total) + " CIGAR words, room for " + std::to_string((long long)cigar_cap);
-		return CHAINDP_ERR_CAPACITY;
-	}
-	if (total == 0) return CHAINDP_OK;
-	if ((rc = ksw_grow(ctx, ctx->ksw_out, (size_t)total * sizeof(uint32_t), "CIGARs", "chaindp_ksw_extd"))) return rc;
-	HIP_TRY(ctx, hipMemcpyAsync(d_off, cigar_off, (N + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-	HIP_TRY(ctx, launch_ksw_pack(st, n, d_prob, d_ez, d_off, (const uint32_t*)ctx->ksw_cig.p, (uint32_t*)ctx->ksw_out.p));
-	HIP_TRY(ctx, hipMemcpyAsync(cigar, ctx->ksw_out.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-	HIP_TRY(ctx, hipStreamSynchronize(st));
-	return CHAINDP_OK;
+	for (size_t i = 0; i < N; ++i) memcpy(ez_out + i * 10, ez.data() + i * KSW_EZ_WORDS, 10 * sizeof(int32_t));
+	const int64_t total = cigar_prefix(ez.data(), KSW_EZ_WORDS, 10, n, cigar_off);
+	return cigar_pack_out(ctx, "chaindp_ksw_extd", cigar_off, n, total, cigar, cigar_cap, v.off, [&](uint32_t *out) {
+		return launch_ksw_pack(st, n, v.prob, v.ez, v.off, v.cig, out);
+	});
 }
 
 // test hook (no GPU needed): what the device routes a problem by -- out = KSW_LDS_BUDGET, then the bytes of state per target base,
@@ -164,8 +179,7 @@ extern "C" int chaindp_ksw_debug_route(chaindp_ctx_t *ctx, int64_t n, int32_t *r
 	if (n == 0) return CHAINDP_OK;
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	std::vector<int32_t> ez((size_t)n * KSW_EZ_WORDS);
-	const int32_t *d_ez = (const int32_t*)((const int64_t*)ctx->ksw_ez.p + 2 + n + 1);
-	HIP_TRY(ctx, hipMemcpyAsync(ez.data(), d_ez, ez.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipMemcpyAsync(ez.data(), ksw_view(ctx, (size_t)n).ez, ez.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	for (int64_t i = 0; i < n; ++i) route[i] = ez[(size_t)i * KSW_EZ_WORDS + 11];
 	return CHAINDP_OK;

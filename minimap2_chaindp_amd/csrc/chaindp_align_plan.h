@@ -3,6 +3,7 @@
 // records the kernels and the host share.  No HIP in here, as chaindp_ksw_plan.h: a stand-alone program runs it under the sanitizers.
 #ifndef CHAINDP_ALIGN_PLAN_H
 #define CHAINDP_ALIGN_PLAN_H
+#include <initializer_list>
 #include "chaindp_ksw_plan.h"
 
 namespace chaindp {
@@ -30,28 +31,43 @@ struct AlignPlan {
 	std::string err;
 };
 
+// ---- the checks chaindp_align1 and chaindp_align1_inv share; who: the call's name and ": ", ahead of every message.  false with err.  The options, up to max_gap:
+inline bool align_check_opt(const AlignOpt *o, int64_t n_reads, const std::string &who, std::string &err)
+{
+	if (!o) { err = who + "NULL options"; return false; }
+	if (n_reads < 0 || n_reads > 0x7fffffff) { err = who + "read count outside 0..2^31 - 1"; return false; }
+	if (o->flag & (AL_F_SR | AL_F_SPLICE)) { err = who + "MM_F_SR and MM_F_SPLICE are not built"; return false; }
+	for (int v : {o->a, o->b, o->q, o->e, o->q2, o->e2})
+		if (v < 0 || v > 127) { err = who + "a, b, q, e, q2, e2 must lie in 0..127"; return false; }
+	if (o->q == o->q2 && o->e == o->e2) { err = who + "q == q2 and e == e2 (ksw_extz2_sse) is not built"; return false; }
+	if (o->max_gap < 0 || o->max_gap > AL_MAX_GAP) { err = who + "max_gap outside 0.." + std::to_string(AL_MAX_GAP); return false; }
+	return true;
+}
+// The per-read offset arrays of n_reads > 0 reads: none NULL, each from 0 and not falling; a read spans less than 2^31 - 1 entries of
+// each of the first n_len of them.  targets_ok: the call's own rule about the targets, looked at between the NULLs and the values.
+inline bool align_check_offsets(int64_t n_reads, std::initializer_list<const int64_t*> offs, size_t n_len, bool targets_ok, const std::string &who, std::string &err)
+{
+	for (const int64_t *off : offs) if (!off) { err = who + "NULL offsets"; return false; }
+	if (!targets_ok) { err = who + "no targets"; return false; }
+	for (const int64_t *off : offs) if (off[0] != 0) { err = who + "offsets must start at 0"; return false; }
+	for (int64_t r = 0; r < n_reads; ++r) {
+		for (const int64_t *off : offs) if (off[r + 1] < off[r]) { err = who + "falling offsets at read " + std::to_string(r); return false; }
+		size_t k = 0;
+		for (const int64_t *off : offs) if (k++ < n_len && off[r + 1] - off[r] >= 0x7fffffff) { err = who + "read " + std::to_string(r) + " is too long"; return false; }
+	}
+	return true;
+}
+
 // 0 and a filled plan, or -1 (CHAINDP_ERR_ARG) with plan.err.  a: x, y pairs; regs: AL_REG_WORDS words per region; t_off: the targets' offsets.
 inline int align_plan(const AlignOpt *o, int64_t n_reads, const int64_t *seq_off, const int64_t *a_off, const uint64_t *a, const int64_t *regs_off,
                       const int32_t *regs, int64_t n_t, const int64_t *t_off, AlignPlan &pl)
 {
 	pl = AlignPlan();
 	const std::string who = "chaindp_align1: ";
-	if (!o) { pl.err = who + "NULL options"; return -1; }
-	if (n_reads < 0 || n_reads > 0x7fffffff) { pl.err = who + "read count outside 0..2^31 - 1"; return -1; }
-	if (o->flag & (AL_F_SR | AL_F_SPLICE)) { pl.err = who + "MM_F_SR and MM_F_SPLICE are not built"; return -1; }
-	for (int v : {o->a, o->b, o->q, o->e, o->q2, o->e2})
-		if (v < 0 || v > 127) { pl.err = who + "a, b, q, e, q2, e2 must lie in 0..127"; return -1; }
-	if (o->q == o->q2 && o->e == o->e2) { pl.err = who + "q == q2 and e == e2 (ksw_extz2_sse) is not built"; return -1; }
-	if (o->max_gap < 0 || o->max_gap > AL_MAX_GAP) { pl.err = who + "max_gap outside 0.." + std::to_string(AL_MAX_GAP); return -1; }
+	if (!align_check_opt(o, n_reads, who, pl.err)) return -1;
 	if (o->bw < 0 || o->bw > (1 << 26) || o->k < 0 || o->k > 255 || o->min_cnt < 0 || o->min_ksw_len < 0) { pl.err = who + "bw, k, min_cnt or min_ksw_len out of range"; return -1; }
 	if (n_reads == 0) { pl.slot_off.assign(1, 0); return 0; }
-	if (!seq_off || !a_off || !regs_off) { pl.err = who + "NULL offsets"; return -1; }
-	if (n_t < 0 || (n_t > 0 && !t_off)) { pl.err = who + "no targets"; return -1; }
-	if (seq_off[0] != 0 || a_off[0] != 0 || regs_off[0] != 0) { pl.err = who + "offsets must start at 0"; return -1; }
-	for (int64_t r = 0; r < n_reads; ++r) {
-		if (seq_off[r + 1] < seq_off[r] || a_off[r + 1] < a_off[r] || regs_off[r + 1] < regs_off[r]) { pl.err = who + "falling offsets at read " + std::to_string(r); return -1; }
-		if (seq_off[r + 1] - seq_off[r] >= 0x7fffffff || a_off[r + 1] - a_off[r] >= 0x7fffffff) { pl.err = who + "read " + std::to_string(r) + " is too long"; return -1; }
-	}
+	if (!align_check_offsets(n_reads, {seq_off, a_off, regs_off}, 2, n_t >= 0 && (n_t == 0 || t_off), who, pl.err)) return -1;
 	pl.n_bases = seq_off[n_reads]; pl.n_anchors = a_off[n_reads]; pl.n_regs = regs_off[n_reads];
 	if (pl.n_regs > 0x7fffffff) { pl.err = who + "more than 2^31 - 1 regions"; return -1; }
 	if ((pl.n_anchors > 0 && !a) || (pl.n_regs > 0 && !regs)) { pl.err = who + "NULL anchors or regions"; return -1; }

@@ -4,6 +4,7 @@
 #define CHAINDP_CTX_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <functional>
 #include <initializer_list>
 #include <string>
 #include <vector>
@@ -95,22 +96,24 @@ struct chaindp_ctx {
 	int n_logf = 0;
 	// reads of several segments: chaindp_frag_post (allocated on first use, grown with the batch)
 	chaindp::DevGrow frag_seq, frag_cnt, frag_u, frag_a, frag_stage, frag_z, frag_stacks, frag_out;
-	// alignment, chaindp_ksw_extd (allocated on first use, grown with the batch): sequences; problem records and their order; counter,
-	// CSR offsets and result words; the workgroups' slices of DP state (global route) and of path matrix; CIGARs as left and as packed
-	chaindp::DevGrow ksw_bases, ksw_prob, ksw_ez, ksw_state, ksw_path, ksw_cig, ksw_out;
+	// alignment, chaindp_ksw_extd (allocated on first use, grown with the batch): sequences; problem records and their order, result
+	// words behind the counters and CSR offsets (both laid out by KswLayout, read through ksw_view); the workgroups' slices of DP state
+	// (global route) and of path matrix; CIGARs as the DP left them
+	chaindp::DevGrow ksw_bases, ksw_prob, ksw_ez, ksw_state, ksw_path, ksw_cig;
+	chaindp::DevGrow cigar_out;                // the packed CIGARs of whichever alignment call ran last (cigar_pack_out): none overlap on a context
 	double ksw_ms = -1;                        // k_ksw_extd's device time in the last call made while profiling was on
 	int ksw_grid_cap = 0;                      // chaindp_ksw_debug_set_grid_cap: at most so many workgroups per DP launch (0: the plan's own)
 	int64_t ksw_launch[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the last plan ksw_reserve saw: count, grid, lds_bytes, path_stride of the two launches (chaindp_ksw_debug_launch)
 	int64_t ksw_n = -1;                        // problems of the last chaindp_ksw_extd whose results are resident (chaindp_ksw_debug_route)
 	// mm_align1, chaindp_align1 (allocated on first use, grown with the batch): the targets' codes and offsets; the reads, anchors and
 	// regions of the batch with their offsets; the regions' plans, problem slots and side records; the first pass's results and CIGARs
-	// kept over the second pass; the Z-drop codes and the second pass's index; the stitched CIGARs, the results, the packed CIGARs
-	chaindp::DevGrow al_tgt, al_toff, al_in, al_reg, al_slot, al_side, al_ez1, al_cig1, al_code, al_stage, al_res, al_out;
+	// kept over the second pass; the Z-drop codes and the second pass's index; the stitched CIGARs
+	chaindp::DevGrow al_tgt, al_toff, al_in, al_reg, al_slot, al_side, al_ez1, al_cig1, al_code, al_stage;
 	std::vector<int64_t> al_t_off;             // the resident targets' offsets (host copy); empty: none set
 	double al_ms[5] = {-1, -1, -1, -1, -1};    // plan, DP, zdrop, stitch, extra of the last chaindp_align1 made while profiling was on
 	// mm_align1_inv, chaindp_align1_inv (allocated on first use, grown with the batch): the reads and regions of the batch with the
-	// candidate list; the per-slot results; the local scores, survivors and their problems; the packed CIGARs
-	chaindp::DevGrow inv_in, inv_res, inv_ll, inv_out;
+	// candidate list; the per-slot results; the local scores, survivors and their problems
+	chaindp::DevGrow inv_in, inv_res, inv_ll;
 	int64_t inv_n = -1;                        // candidates of the last chaindp_align1_inv whose local scores are resident (chaindp_align_inv_debug_ll)
 	double inv_ms[4] = {-1, -1, -1, -1};       // local score, gather + DP, finish + skip, pack of the last call made while profiling was on
 	int frag_lds_cap = FRAG_LDS_CAP;           // chaindp_debug_set_frag_lds_cap (tests): fewer hits per fragment stay in LDS
@@ -189,10 +192,29 @@ int post_require_hits(chaindp_ctx *ctx, const char *who);
 int post_stage_rep_len(chaindp_ctx *ctx, const int32_t *rep_len, int64_t R, const int32_t **d_rep);
 int post_finish(chaindp_ctx *ctx);
 
-// chaindp_abi_ksw.cpp: the parts of chaindp_ksw_extd that chaindp_align1 runs on records its own kernels made
+// chaindp_abi_ksw.cpp: the host scaffold of the alignment stages (chaindp_ksw_extd, chaindp_align1, chaindp_align1_inv, and any new one)
 int ksw_grow(chaindp_ctx *ctx, DevGrow &g, size_t need, const char *what, const char *who);
 int ksw_reserve(chaindp_ctx *ctx, const KswPlan &pl, int64_t n_bases, const char *who);
-int ksw_dispatch(chaindp_ctx *ctx, const KswPlan &pl, hipEvent_t ev0, hipEvent_t ev1);
+// where the DP's records and results for N problems lie on the device (KswLayout over ksw_prob and ksw_ez), and its CIGAR staging
+struct KswView { KswProb *prob; int32_t *order; unsigned int *counter; int64_t *off; int32_t *ez; uint32_t *cig; };
+KswView ksw_view(const chaindp_ctx *ctx, size_t N);
+// While profiling is on: an event at every boundary between the stages of a call; destroyed on every way out of it.
+struct StageEvents {
+	explicit StageEvents(chaindp_ctx *c) : ctx(c) {}
+	StageEvents(const StageEvents&) = delete;
+	~StageEvents();
+	hipError_t mark(int stage);      // the time since the last mark belongs to `stage` (-1: host time, not counted); nothing while profiling is off
+	int fold(double *ms, int n);     // with any mark made: ms[0..n) = the milliseconds of every stage, ms[] untouched otherwise
+	chaindp_ctx *ctx;
+	std::vector<hipEvent_t> e;
+	std::vector<int> stage;          // the stage that ends at e[k]
+};
+// the records and their order up, the two launches; the bases are on the device already.  ev (or null): the launches alone are its stage 0
+int ksw_dispatch(chaindp_ctx *ctx, const KswPlan &pl, StageEvents *ev);
+// The end of a call that returns CIGARs: cigar_off[0..n] is filled and sums to total.  Refuses a total above cigar_cap
+// (CHAINDP_ERR_CAPACITY); else offsets up to d_off, launch(out) packs into cigar_out, the words come down into cigar, the stream is idle.
+int cigar_pack_out(chaindp_ctx *ctx, const char *who, const int64_t *cigar_off, int64_t n, int64_t total, uint32_t *cigar, int64_t cigar_cap,
+                   int64_t *d_off, const std::function<hipError_t(uint32_t *out)> &launch);
 
 // ---- stage entry points that other stages call
 int collect_seeds_impl(chaindp_ctx *ctx, const chaindp_index_t *ix, int flag, int max_occ, int64_t n_reads,

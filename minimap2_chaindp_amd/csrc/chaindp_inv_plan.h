@@ -38,22 +38,10 @@ inline int inv_plan(const AlignOpt *o, int64_t n_reads, const int64_t *seq_off, 
 {
 	pl = InvPlan();
 	const std::string who = "chaindp_align1_inv: ";
-	if (!o) { pl.err = who + "NULL options"; return -1; }
-	if (n_reads < 0 || n_reads > 0x7fffffff) { pl.err = who + "read count outside 0..2^31 - 1"; return -1; }
-	if (o->flag & (AL_F_SR | AL_F_SPLICE)) { pl.err = who + "MM_F_SR and MM_F_SPLICE are not built"; return -1; }
-	for (int v : {o->a, o->b, o->q, o->e, o->q2, o->e2})
-		if (v < 0 || v > 127) { pl.err = who + "a, b, q, e, q2, e2 must lie in 0..127"; return -1; }
-	if (o->q == o->q2 && o->e == o->e2) { pl.err = who + "q == q2 and e == e2 (ksw_extz2_sse) is not built"; return -1; }
-	if (o->max_gap < 0 || o->max_gap > AL_MAX_GAP) { pl.err = who + "max_gap outside 0.." + std::to_string(AL_MAX_GAP); return -1; }
+	if (!align_check_opt(o, n_reads, who, pl.err)) return -1;
 	if (o->bw < 0 || o->bw > (1 << 26)) { pl.err = who + "bw out of range"; return -1; }
 	if (n_reads == 0) return 0;
-	if (!seq_off || !regs_off) { pl.err = who + "NULL offsets"; return -1; }
-	if (n_t <= 0 || !t_off) { pl.err = who + "no targets"; return -1; }
-	if (seq_off[0] != 0 || regs_off[0] != 0) { pl.err = who + "offsets must start at 0"; return -1; }
-	for (int64_t r = 0; r < n_reads; ++r) {
-		if (seq_off[r + 1] < seq_off[r] || regs_off[r + 1] < regs_off[r]) { pl.err = who + "falling offsets at read " + std::to_string(r); return -1; }
-		if (seq_off[r + 1] - seq_off[r] >= 0x7fffffff) { pl.err = who + "read " + std::to_string(r) + " is too long"; return -1; }
-	}
+	if (!align_check_offsets(n_reads, {seq_off, regs_off}, 1, n_t > 0 && t_off, who, pl.err)) return -1;
 	pl.n_bases = seq_off[n_reads]; pl.n_slots = regs_off[n_reads];
 	if (pl.n_slots > 0x7fffffff) { pl.err = who + "more than 2^31 - 1 regions"; return -1; }
 	if (pl.n_slots > 0 && !regs) { pl.err = who + "NULL regions"; return -1; }

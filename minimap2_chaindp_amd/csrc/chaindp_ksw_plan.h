@@ -1,6 +1,7 @@
 // chaindp_ksw_plan.h -- what the host decides about a batch of chaindp_ksw_extd before anything touches the device: the argument checks,
-// the per-problem records, the order they are taken in and the sizes of every buffer.  No HIP in here: the kernels' translation unit
-// takes the constants and the record from it, the host ABI the plan, and a stand-alone program runs the plan under the sanitizers.
+// the per-problem records, the order they are taken in and the sizes of every buffer; and, at the end, what the alignment stages share of
+// their host side (buffer layout, CIGAR offsets).  No HIP in here: the kernels' translation unit takes the constants and the record from
+// it, the host ABI the plan, and a stand-alone program runs the plan under the sanitizers.
 #ifndef CHAINDP_KSW_PLAN_H
 #define CHAINDP_KSW_PLAN_H
 #include <stddef.h>
@@ -157,6 +158,38 @@ inline int ksw_plan(int64_t n, const uint8_t *bases, const int64_t *q_beg, const
 	}
 	ksw_plan_route(pl, cus, grid_cap);
 	return 0;
+}
+
+// ---- what the alignment stages (chaindp_ksw_extd, chaindp_align1, chaindp_align1_inv) share of their host side
+struct Carve {                       // consecutive 16-byte aligned pieces of one buffer
+	size_t at = 0;
+	size_t take(size_t bytes) { const size_t o = at; at += (bytes + 15) / 16 * 16; return o; }
+};
+
+// The DP's two buffers for N problems, in bytes: ksw_reserve takes the sizes from here, every reader (ksw_view) the offsets.  ksw_prob: the N
+// records, then the N order words.  ksw_ez: the two launches' counters (8 bytes each), the N + 1 CSR offsets, the N x KSW_EZ_WORDS result words.
+struct KswLayout {
+	size_t order, prob_bytes;        // ksw_prob: where the order words start (the records start the buffer), the buffer's size
+	size_t off, ez, ez_bytes;        // ksw_ez: where the CSR offsets and the result words start (the counters start the buffer), its size
+	explicit KswLayout(size_t N)
+		: order(N * sizeof(KswProb)), prob_bytes(order + N * sizeof(int32_t) + 16), off(2 * sizeof(int64_t)),
+		  ez(off + (N + 1) * sizeof(int64_t)), ez_bytes(ez + N * KSW_EZ_WORDS * sizeof(int32_t) + 16) {}
+};
+
+// The end of a call that returns CIGARs.  The counts are word `at` of every `stride` words of cnt (ez: word 10 at stride KSW_EZ_WORDS;
+// chaindp_align_extra_t: word 4 at stride 5): cigar_off[0..n] becomes their running sum, the total is returned.
+inline int64_t cigar_prefix(const int32_t *cnt, size_t stride, size_t at, int64_t n, int64_t *cigar_off)
+{
+	cigar_off[0] = 0;
+	for (int64_t i = 0; i < n; ++i) cigar_off[i + 1] = cigar_off[i] + cnt[(size_t)i * stride + at];
+	return cigar_off[n];
+}
+// ... and whether the caller's array holds them: false with the refusal's text in err (CHAINDP_ERR_CAPACITY)
+inline bool cigar_room(const char *who, int64_t total, int64_t cap, std::string &err)
+{
+	if (total <= cap) return true;
+	err = std::string(who) + ": " + std::to_string((long long)total) + " CIGAR words, room for " + std::to_string((long long)cap);
+	return false;
 }
 
 } // namespace chaindp

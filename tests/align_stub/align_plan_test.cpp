@@ -76,6 +76,49 @@ int main()
 	{ Batch b = base; b.t_off.resize(1); refuse(b); }                              // no targets
 	assert(align_plan(nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, pl) == -1); ++refused;
 	{ Batch b = base; b.o.flag = 0x100000; assert(b.plan(pl) == 0); }              // MM_F_FOR_ONLY is allowed
+	// the checks shared with chaindp_align1_inv (align_check_opt, align_check_offsets): every refusal's text, under this call's name
+	auto says = [&](const Batch &b, const char *text) { assert(b.plan(pl) == -1 && pl.err == text); ++refused; };
+	assert(pl.err.empty() && align_plan(nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, pl) == -1 && pl.err == "chaindp_align1: NULL options");
+	for (int64_t n : {(int64_t)-1, (int64_t)1 << 31}) {
+		assert(align_plan(&base.o, n, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, pl) == -1 && pl.err == "chaindp_align1: read count outside 0..2^31 - 1");
+		++refused;
+	}
+	{ Batch b = base; b.o.flag = AL_F_SR; says(b, "chaindp_align1: MM_F_SR and MM_F_SPLICE are not built"); }
+	{ Batch b = base; b.o.flag = AL_F_SPLICE; b.o.a = -1; says(b, "chaindp_align1: MM_F_SR and MM_F_SPLICE are not built"); }   // the flag before the scoring
+	for (int k = 0; k < 6; ++k) for (int v : {-1, 128}) { Batch b = base; (&b.o.a)[k] = v; says(b, "chaindp_align1: a, b, q, e, q2, e2 must lie in 0..127"); }
+	{ Batch b = base; b.o.q2 = b.o.q; b.o.e2 = b.o.e; b.o.max_gap = -1; says(b, "chaindp_align1: q == q2 and e == e2 (ksw_extz2_sse) is not built"); }
+	for (int v : {-1, AL_MAX_GAP + 1}) { Batch b = base; b.o.max_gap = v; b.o.bw = -1; says(b, "chaindp_align1: max_gap outside 0..20000"); }
+	{ Batch b = base; b.o.max_gap = AL_MAX_GAP; assert(b.plan(pl) == 0); }
+	// ... what only this call checks of its options comes behind them, and before the offsets
+	for (int f = 0; f < 6; ++f) {
+		Batch b = base; b.t_off.resize(1);
+		(f == 0 ? b.o.bw : f == 1 ? b.o.k : f == 2 ? b.o.min_cnt : f == 3 ? b.o.min_ksw_len : f == 4 ? b.o.bw : b.o.k) = f == 4 ? (1 << 26) + 1 : f == 5 ? 256 : -1;
+		says(b, "chaindp_align1: bw, k, min_cnt or min_ksw_len out of range");
+	}
+	{
+		const int64_t zero[3] = {0, 0, 0}, one[3] = {1, 1, 1}, fall[3] = {0, 5, 4}, big[3] = {0, 0x7fffffff, 0x7fffffff}, ok[3] = {0, 0x7ffffffe, 0x7ffffffe},
+		              late[3] = {0, 0, 0x7fffffff};
+		auto direct = [&](const int64_t *so, const int64_t *ao, const int64_t *ro, int64_t n_t, const int64_t *to, const char *text) {
+			assert(align_plan(&base.o, 2, so, ao, nullptr, ro, nullptr, n_t, to, pl) == -1 && pl.err == text); ++refused;
+		};
+		direct(nullptr, zero, zero, 0, zero, "chaindp_align1: NULL offsets");
+		direct(zero, nullptr, zero, 0, zero, "chaindp_align1: NULL offsets");
+		direct(zero, zero, nullptr, -1, nullptr, "chaindp_align1: NULL offsets");      // ... before the targets are looked at
+		direct(one, zero, zero, -1, zero, "chaindp_align1: no targets");              // ... and those before the offsets' values
+		direct(zero, zero, zero, 1, nullptr, "chaindp_align1: no targets");
+		direct(one, zero, zero, 0, nullptr, "chaindp_align1: offsets must start at 0");     // this call's rule: no target at all is none missing
+		direct(zero, one, zero, 1, zero, "chaindp_align1: offsets must start at 0");
+		direct(zero, zero, one, 1, zero, "chaindp_align1: offsets must start at 0");
+		direct(fall, zero, zero, 1, zero, "chaindp_align1: falling offsets at read 1");
+		direct(zero, fall, zero, 1, zero, "chaindp_align1: falling offsets at read 1");
+		direct(late, zero, fall, 1, zero, "chaindp_align1: falling offsets at read 1");     // a read's fall before its length
+		direct(big, zero, fall, 1, zero, "chaindp_align1: read 0 is too long");            // ... read by read
+		direct(big, zero, zero, 1, zero, "chaindp_align1: read 0 is too long");
+		direct(zero, big, zero, 1, zero, "chaindp_align1: read 0 is too long");
+		direct(fall, big, zero, 1, zero, "chaindp_align1: read 0 is too long");
+		direct(zero, zero, big, 1, zero, "chaindp_align1: NULL anchors or regions");   // regions are not counted per read: 2^31 - 1 of them pass the offsets
+		direct(ok, ok, zero, 1, zero, "chaindp_align1: NULL anchors or regions");      // one below the limit passes them too
+	}
 	// seeded batches: slots, then the compact list and the DP plan from records a planning kernel could have left
 	std::mt19937 rng(11);
 	for (int t = 0; t < 30; ++t) {

@@ -100,6 +100,41 @@ int main()
 	{ Batch b = base; assert(inv_plan(nullptr, 3, nullptr, nullptr, nullptr, 0, nullptr, pl) == -1); ++refused; (void)b; }
 	{ Batch b = base; auto so = exact(b.seq_off), ro = exact(b.regs_off), to = exact(b.t_off);
 	  assert(inv_plan(&b.o, 3, so.get(), ro.get(), nullptr, 2, to.get(), pl) == -1); ++refused; }                  // NULL regions
+	// the checks shared with chaindp_align1 (align_check_opt, align_check_offsets): every refusal's text, under this call's name
+	auto says = [&](const Batch &b, const char *text) { assert(b.plan(pl) == -1 && pl.err == text); ++refused; };
+	assert(inv_plan(nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, pl) == -1 && pl.err == "chaindp_align1_inv: NULL options"); ++refused;
+	for (int64_t n : {(int64_t)-1, (int64_t)1 << 31}) {
+		assert(inv_plan(&base.o, n, nullptr, nullptr, nullptr, 0, nullptr, pl) == -1 && pl.err == "chaindp_align1_inv: read count outside 0..2^31 - 1");
+		++refused;
+	}
+	{ Batch b = base; b.o.flag = AL_F_SR; says(b, "chaindp_align1_inv: MM_F_SR and MM_F_SPLICE are not built"); }
+	{ Batch b = base; b.o.flag = AL_F_SPLICE; b.o.a = -1; says(b, "chaindp_align1_inv: MM_F_SR and MM_F_SPLICE are not built"); }   // the flag before the scoring
+	for (int k = 0; k < 6; ++k) for (int v : {-1, 128}) { Batch b = base; (&b.o.a)[k] = v; says(b, "chaindp_align1_inv: a, b, q, e, q2, e2 must lie in 0..127"); }
+	{ Batch b = base; b.o.q2 = b.o.q; b.o.e2 = b.o.e; b.o.max_gap = -1; says(b, "chaindp_align1_inv: q == q2 and e == e2 (ksw_extz2_sse) is not built"); }
+	for (int v : {-1, AL_MAX_GAP + 1}) { Batch b = base; b.o.max_gap = v; b.o.bw = -1; says(b, "chaindp_align1_inv: max_gap outside 0..20000"); }
+	// ... what only this call checks of its options comes behind them, and before the offsets; k, min_cnt and min_ksw_len are not its own
+	for (int v : {-1, (1 << 26) + 1}) { Batch b = base; b.t_off = {0}; b.o.bw = v; says(b, "chaindp_align1_inv: bw out of range"); }
+	{ Batch b = base; b.o.k = -1; b.o.min_cnt = -1; b.o.min_ksw_len = -1; assert(b.plan(pl) == 0 && pl.cand.size() == 3); ++planned; }
+	{
+		const int64_t zero[3] = {0, 0, 0}, one[3] = {1, 1, 1}, fall[3] = {0, 5, 4}, big[3] = {0, 0x7fffffff, 0x7fffffff}, ok[3] = {0, 0x7ffffffe, 0x7ffffffe},
+		              late[3] = {0, 0, 0x7fffffff};
+		auto direct = [&](const int64_t *so, const int64_t *ro, int64_t n_t, const int64_t *to, const char *text) {
+			assert(inv_plan(&base.o, 2, so, ro, nullptr, n_t, to, pl) == -1 && pl.err == text); ++refused;
+		};
+		direct(nullptr, zero, 1, zero, "chaindp_align1_inv: NULL offsets");
+		direct(zero, nullptr, 0, nullptr, "chaindp_align1_inv: NULL offsets");         // ... before the targets are looked at
+		direct(one, zero, 0, zero, "chaindp_align1_inv: no targets");                 // this call's rule: it needs a target; before the offsets' values
+		direct(one, zero, -1, zero, "chaindp_align1_inv: no targets");
+		direct(zero, zero, 1, nullptr, "chaindp_align1_inv: no targets");
+		direct(one, zero, 1, zero, "chaindp_align1_inv: offsets must start at 0");
+		direct(zero, one, 1, zero, "chaindp_align1_inv: offsets must start at 0");
+		direct(fall, zero, 1, zero, "chaindp_align1_inv: falling offsets at read 1");
+		direct(late, fall, 1, zero, "chaindp_align1_inv: falling offsets at read 1");  // a read's fall before its length
+		direct(big, fall, 1, zero, "chaindp_align1_inv: read 0 is too long");         // ... read by read
+		direct(zero, fall, 1, zero, "chaindp_align1_inv: falling offsets at read 1");
+		direct(zero, big, 1, zero, "chaindp_align1_inv: NULL regions");               // regions are not counted per read: 2^31 - 1 of them pass the offsets
+		direct(ok, big, 1, zero, "chaindp_align1_inv: NULL regions");                 // a read one below the limit passes them too
+	}
 	// a refused pair that returns early is no refusal: its rid is never looked at
 	{ Batch b = base; b.regs[2] = b.regs[AL_REG_WORDS + 2] = 9; b.regs[AL_REG_WORDS + 15] &= ~(int32_t)INV_BIT_SPLIT_INV; assert(b.plan(pl) == 0 && pl.cand.size() == 2); ++planned; }
 	// seeded batches: the candidates in slot order, the problems of the survivors inside their stretches, the DP's plan over them

@@ -178,6 +178,54 @@ int main()
 		check_plan(b, pc, 256, 3);
 		++halved;
 	}
-	printf("ksw plan ok: %d batches planned, %d calls refused; %d plans under a grid cap, %d with a halved grid\n", planned, refused, capped, halved);
+	// what the alignment stages share of their host side.  The DP's buffers for N problems: the offsets and sizes as the stages spelled
+	// them out before there was a description
+	int layouts = 0;
+	for (size_t N : {0, 1, 2, 63, 64, 65, 4160}) {
+		const KswLayout lay(N);
+		assert(lay.order == N * sizeof(KswProb) && lay.off == 2 * 8 && lay.ez == (2 + N + 1) * 8);
+		assert(lay.prob_bytes == N * sizeof(KswProb) + N * 4 + 16);
+		assert(lay.ez_bytes == N * KSW_EZ_WORDS * 4 + (N + 1) * 8 + 32);
+		assert(lay.order + N * 4 <= lay.prob_bytes && lay.ez + N * KSW_EZ_WORDS * 4 <= lay.ez_bytes && lay.order % 8 == 0 && lay.ez % 8 == 0);
+		// pieces of N-dependent sizes, one of them empty: 16-byte aligned, in order, none reaching into the next
+		Carve c;
+		const size_t bytes[] = {(N + 1) * 8, N * 4, 0, N * sizeof(KswProb), 1, N * 20, 17};
+		size_t end = 0;
+		for (size_t b : bytes) {
+			const size_t o = c.take(b);
+			assert(o % 16 == 0 && o >= end && o < end + 16 && c.at >= o + b && c.at % 16 == 0 && c.at < o + b + 16);
+			end = o + b;
+		}
+		// the CIGAR offsets from the counts, as ez keeps them (word 10 of KSW_EZ_WORDS) and as chaindp_align_extra_t does (word 4 of 5)
+		const size_t strides[2][2] = {{KSW_EZ_WORDS, 10}, {5, 4}};
+		for (const auto &sa : strides) {
+			std::unique_ptr<int32_t[]> cnt(new int32_t[N * sa[0] + 1]);
+			std::unique_ptr<int64_t[]> off(new int64_t[N + 1]);
+			for (size_t i = 0; i < N * sa[0] + 1; ++i) cnt[i] = -1000000;              // a word that is no count spoils the sum
+			int64_t sum = 0;
+			for (size_t i = 0; i < N; ++i) sum += cnt[i * sa[0] + sa[1]] = (int32_t)(rng() % 3 ? rng() % 5000 : 0);
+			for (size_t i = 0; i <= N; ++i) off[i] = -1;
+			assert(cigar_prefix(cnt.get(), sa[0], sa[1], (int64_t)N, off.get()) == sum && off[0] == 0 && off[N] == sum);
+			for (size_t i = 0; i < N; ++i) assert(off[i + 1] - off[i] == cnt[i * sa[0] + sa[1]]);
+			// room for exactly that many words is room enough; one word less is the refusal, in the words of each of the three calls
+			std::string err = "untouched";
+			assert(cigar_room("chaindp_ksw_extd", sum, sum, err) && cigar_room("chaindp_align1", sum, sum + 1, err) && err == "untouched");
+			for (const char *who : {"chaindp_ksw_extd", "chaindp_align1", "chaindp_align1_inv"}) {
+				assert(!cigar_room(who, sum + 1, sum, err));
+				assert(err == std::string(who) + ": " + std::to_string((long long)(sum + 1)) + " CIGAR words, room for " + std::to_string((long long)sum));
+				++refused;
+			}
+		}
+		++layouts;
+	}
+	{
+		std::string err;
+		assert(!cigar_room("chaindp_ksw_extd", 13, 12, err) && err == "chaindp_ksw_extd: 13 CIGAR words, room for 12");
+		assert(!cigar_room("chaindp_align1", 4097, 4096, err) && err == "chaindp_align1: 4097 CIGAR words, room for 4096");
+		assert(!cigar_room("chaindp_align1_inv", 1, 0, err) && err == "chaindp_align1_inv: 1 CIGAR words, room for 0");
+		assert(cigar_room("chaindp_align1_inv", 0, 0, err));
+	}
+	printf("ksw plan ok: %d batches planned, %d calls refused; %d plans under a grid cap, %d with a halved grid; %d buffer layouts\n", planned, refused, capped,
+	       halved, layouts);
 	return 0;
 }

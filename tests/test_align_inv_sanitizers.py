@@ -26,4 +26,4 @@ def test_inv_plan_is_clean_under_sanitizers(tmp_path):
     r = subprocess.run([os.path.join(HERE, "inv_plan_asan")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120, env=env)
     assert r.returncode == 0, r.stdout[-3000:]
     assert "ERROR: AddressSanitizer" not in r.stdout and "LeakSanitizer" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-3000:]
-    assert "inv plan ok: 28 batches planned, 16 calls refused" in r.stdout, r.stdout[-3000:]
+    assert "inv plan ok: 29 batches planned, 51 calls refused" in r.stdout, r.stdout[-3000:]

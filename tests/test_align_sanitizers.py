@@ -26,4 +26,4 @@ def test_align_plan_is_clean_under_sanitizers(tmp_path):
     r = subprocess.run([os.path.join(HERE, "align_plan_asan")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120, env=env)
     assert r.returncode == 0, r.stdout[-3000:]
     assert "ERROR: AddressSanitizer" not in r.stdout and "LeakSanitizer" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-3000:]
-    assert "align plan ok: 30 batches planned, 18 calls refused" in r.stdout, r.stdout[-3000:]
+    assert "align plan ok: 30 batches planned, 60 calls refused" in r.stdout, r.stdout[-3000:]

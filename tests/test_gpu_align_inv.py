@@ -203,3 +203,68 @@ def test_refusals_leave_the_context_usable(dev):
     with pytest.raises(chaindp.ChainDPError, match="target"):
         dev.align1_inv(opt_of(g), g["seq_off"], g["seq"], g["regs_off"], g["regs"])
     check(dev, g, call(dev, g))
+
+
+# ---- the three alignment stages on one context: what they share on the host (the packed-CIGAR buffer, the stage events)
+def stage_calls(dev):
+    """name -> a function that makes one call of the stage on `scene` and checks every word of its result."""
+    import test_gpu_align as TA
+    import test_gpu_ksw as T
+
+    def ksw(scene):
+        k = T.load(scene)
+        T.check(k, *T.call(dev, k))
+
+    def align(scene):
+        a = TA.load(scene)
+        TA.check(a, TA.call(dev, a))
+
+    def inv(scene):
+        g = load(scene)
+        check(dev, g, call(dev, g))
+    return dict(ksw_extd=ksw, align1=align, align1_inv=inv)
+
+
+@pytest.fixture()
+def fresh():
+    from minimap2_chaindp_amd import chaindp
+    with chaindp.Device(0, max_anchors=1 << 16, max_reads=1 << 10) as d:
+        yield d
+
+
+def test_one_packed_cigar_buffer_serves_the_three_stages_in_any_order(fresh):
+    """Small after large, large after small (the buffer grows) and a call that packs nothing after one that did."""
+    run = stage_calls(fresh)
+    order = [("ksw_extd", "fuzz_asm10"), ("align1_inv", "no_cigar"), ("align1", "fuzz"), ("align1_inv", "fuzz"), ("ksw_extd", "named_early")]
+    assert int(load("no_cigar")["cigar_off"][-1]) == 0
+    for stage, scene in order + order[::-1]:
+        run[stage](scene)
+
+
+def test_alignment_stages_hold_their_memory_steady(fresh):
+    run = stage_calls(fresh)
+    held = []
+    for _ in range(4):
+        run["ksw_extd"]("fuzz_asm10"); run["align1"]("fuzz"); run["align1_inv"]("fuzz")
+        held.append(fresh.device_bytes())
+    print("device_bytes after each round of ksw_extd, align1, align1_inv:", held)
+    assert held[1] == held[3], held
+
+
+def test_stage_ms_hooks_follow_the_profiling_switch(fresh):
+    run = stage_calls(fresh)
+    scenes = dict(ksw_extd="fuzz_asm10", align1="fuzz", align1_inv="fuzz")
+    ms = lambda: dict(ksw_extd=[fresh.ksw_ms()], align1=list(fresh.align_ms().values()), align1_inv=list(fresh.align_inv_ms().values()))
+    before = ms()
+    assert [len(v) for v in before.values()] == [1, 5, 4] and all(x == -1 for v in before.values() for x in v), before
+    fresh.set_profiling(True)
+    for stage, scene in scenes.items():
+        run[stage](scene)
+        after = ms()
+        assert all(np.isfinite(x) and x >= 0 for x in after[stage]), (stage, after)
+        assert all(after[s] == before[s] for s in scenes if s != stage), (stage, before, after)
+        before = after
+    fresh.set_profiling(False)
+    for stage, scene in scenes.items():
+        run[stage](scene)
+    assert ms() == before

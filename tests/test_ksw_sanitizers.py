@@ -27,4 +27,4 @@ def test_alignment_plan_is_clean_under_sanitizers(tmp_path):
     r = subprocess.run([os.path.join(HERE, "ksw_plan_asan")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120, env=env)
     assert r.returncode == 0, r.stdout[-3000:]
     assert "ERROR: AddressSanitizer" not in r.stdout and "LeakSanitizer" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-3000:]
-    assert "ksw plan ok: 40 batches planned" in r.stdout, r.stdout[-3000:]
+    assert "ksw plan ok: 40 batches planned, 85 calls refused" in r.stdout and "; 7 buffer layouts" in r.stdout, r.stdout[-3000:]
