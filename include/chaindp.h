@@ -431,4 +431,5 @@ int chaindp_set_variant(chaindp_ctx_t *ctx, int force_general);
 #include "chaindp_ksw.h"
 #include "chaindp_align.h"
 #include "chaindp_align_inv.h"
+#include "chaindp_align_reads.h"
 #endif

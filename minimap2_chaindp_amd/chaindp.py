@@ -33,6 +33,8 @@ KSW_EZ_FIELDS = ("max", "zdropped", "max_q", "max_t", "mqe", "mqe_t", "mte", "mt
 ALIGN_SYMBOLS = tuple(_cabi.prototypes("chaindp_align.h"))
 # ... and for mm_align1_inv
 ALIGN_INV_SYMBOLS = tuple(_cabi.prototypes("chaindp_align_inv.h"))
+# ... and for mm_align_skeleton
+ALIGN_READS_SYMBOLS = tuple(_cabi.prototypes("chaindp_align_reads.h"))
 ALIGN_EXTRA_DTYPE = np.dtype([(k, "<i4") for k in ("has_extra", "dp_score", "dp_max", "n_ambi", "n_cigar")])   # chaindp_align_extra_t
 ERR_CAPACITY = -2
 
@@ -49,14 +51,15 @@ _lib = None
 
 
 def lib():
-    """The library, every function of include/chaindp.h, chaindp_gaps.h, chaindp_ksw.h, chaindp_align.h, chaindp_align_inv.h and chaindp_debug.h bound with the
+    """The library, every function of include/chaindp.h, chaindp_gaps.h, chaindp_ksw.h, chaindp_align.h, chaindp_align_inv.h, chaindp_align_reads.h and chaindp_debug.h bound with the
     header's prototype."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise ChainDPError(f"{LIB_PATH} is missing: build it with __graft_entry__.build() "
                                "(make -C minimap2_chaindp_amd/csrc); there is no fallback path")
-        _lib = _cabi.bind(C.CDLL(LIB_PATH), "chaindp.h", "chaindp_gaps.h", "chaindp_ksw.h", "chaindp_align.h", "chaindp_align_inv.h", "chaindp_debug.h")
+        _lib = _cabi.bind(C.CDLL(LIB_PATH), "chaindp.h", "chaindp_gaps.h", "chaindp_ksw.h", "chaindp_align.h", "chaindp_align_inv.h", "chaindp_align_reads.h",
+                          "chaindp_debug.h")
     return _lib
 
 
@@ -115,6 +118,10 @@ _CAPS = {
     # _cigars: the room is for CIGAR words, not hits.  align1: a guess of one word per four read bases, the whole call again with the exact count
     "align1":        _Cap("n_bases", 4,  True,  "raise", "again",      None),
     "align1_inv":    _Cap("n_bases", 4,  True,  "raise", "again",      None),      # the same for the inversions' CIGAR words
+    # align_reads has both kinds of room: final regions (a guess of twice the input regions) and their CIGAR words.  The result stays
+    # resident, so a guess that was short is made good by the fetch call, nothing is computed again
+    "align_reads":       _Cap("n_regs2", 1, True, "raise", "align_reads_fetch", None),
+    "align_reads_cigar": _Cap("n_bases", 4, True, "raise", "align_reads_fetch", None),
     "ksw_extd":      _Cap("n_span",  1,  False, "raise", None,         None),      # room for q_len + t_len words a problem: never short
 }
 
@@ -631,6 +638,83 @@ class Device:
             return self._lib.chaindp_align1_inv(self._ctx, C.byref(opt), n_reads, _ptr(seq_off), _ptr0(seq), _ptr(regs_off), _ptr0(regs_in), _ptr0(made),
                                                 _ptr0(r_inv), _ptr0(extra), _ptr(off), cigar, cap)
         return self._cigars("align1_inv", cigar_cap, alloc, call, ("made", "r_inv", "extra", "cigar_off"), n_bases=len(seq))
+
+    # -- whole reads: mm_align_skeleton's loop around the two stages (chaindp_align_reads)
+    def align_reads(self, opt, seq_off, seq, a_off, a, regs_off, regs, regs_cap=None, cigar_cap=None):
+        """mm_align_skeleton for every read (chaindp_align_reads): the inputs of align1; every round of align1, the inversions, mm_filter_regs
+        and mm_hit_sort_by_dp happen in the one call, bases, anchors and CIGAR words staying on the device between the rounds.  Nothing is
+        changed in place.  Returns (a, regs_off int64[n_reads + 1], regs REG_DTYPE[...], extra ALIGN_EXTRA_DTYPE[...], cigar_off
+        int64[len(regs) + 1], cigar uint32[...]): the anchors with their MM_SEED_IGNORE marks and each read's final regions in
+        mm_hit_sort_by_dp's order with their CIGARs.  regs_cap / cigar_cap None: a guess, and where it was short the resident result
+        fetched with the exact room (the _CAPS rows); a cap of the caller's that is too small raises ChainDPError and err.a / .regs_off /
+        .need hold what the C call filled in (need: final regions, CIGAR words)."""
+        (seq, seq_off), a_off, regs_off = self._seqs(seq, seq_off), _arr(a_off, np.int64), _arr(regs_off, np.int64)
+        a_out, regs_in = _arr(a, np.uint64).reshape(-1, 2).copy(), _arr(regs, REG_DTYPE)
+        n_reads, n_regs = len(seq_off) - 1, len(regs_in)
+        if len(a_off) != n_reads + 1 or len(regs_off) != n_reads + 1 or int(a_off[-1]) != len(a_out) or int(regs_off[-1]) != n_regs or int(seq_off[-1]) != len(seq):
+            raise ValueError("seq_off, a_off and regs_off need one entry per read and one more, and must end at the sizes of seq, a and regs")
+        size = dict(n_regs2=2 * n_regs, n_bases=len(seq))
+        given = (regs_cap, cigar_cap)
+        caps = [int(c) if c is not None else max(size[row.source] // row.divisor, REGS_CAP_FLOOR if row.floored else 1)
+                for c, row in zip(given, (_CAPS["align_reads"], _CAPS["align_reads_cigar"]))]
+        out_off, need = np.zeros(n_reads + 1, np.int64), np.zeros(2, np.int64)
+
+        def outputs():
+            return (np.zeros(max(caps[0], 1), REG_DTYPE), np.zeros(max(caps[0], 1), ALIGN_EXTRA_DTYPE), np.zeros(max(caps[0], 0) + 1, np.int64),
+                    np.zeros(max(caps[1], 1), np.uint32))
+
+        def room(o):
+            return _ptr(out_off), _ptr(o[0]), _ptr(o[1]), caps[0], _ptr(o[2]), _ptr(o[3]), caps[1], _ptr(need)
+        o = outputs()
+        rc = self._lib.chaindp_align_reads(self._ctx, C.byref(opt), n_reads, _ptr(seq_off), _ptr0(seq), _ptr(a_off), _ptr0(a_out), _ptr(regs_off),
+                                           _ptr0(regs_in), *room(o))
+        if rc == 0 or (rc == ERR_CAPACITY and (int(need[0]) > caps[0] or int(need[1]) > caps[1])):   # a result is resident: a call refused
+            # at its entry leaves the one before, one that ran out of device memory leaves none and says nothing of need
+            self._align_reads_n = n_reads
+        if rc == ERR_CAPACITY and (int(need[0]) > caps[0] or int(need[1]) > caps[1]):
+            if any(c is not None and int(n) > cap for c, n, cap in zip(given, need, caps)):
+                err = ChainDPError(f"chaindp error {rc}: {self._lib.chaindp_last_error(self._ctx).decode()}")
+                err.__dict__.update(a=a_out, regs_off=out_off, need=need)
+                raise err
+            caps = [max(cap, int(n)) for cap, n in zip(caps, need)]
+            o = outputs()
+            rc = getattr(self._lib, "chaindp_" + _CAPS["align_reads"].retry)(self._ctx, n_reads, *room(o))
+        self._check(rc)
+        n, m = int(need[0]), int(need[1])
+        return a_out, out_off, o[0][:n], o[1][:n], o[2][:n + 1], o[3][:m]
+
+    def align_reads_placed(self):
+        """Each read's list of the last align_reads as it stood ahead of mm_filter_regs, split-off regions and inversions in their places
+        (test hook): (placed_off int64[n_reads + 1], placed REG_DTYPE[...])."""
+        n_reads = getattr(self, "_align_reads_n", 0)             # the reads of the last align_reads; the C side refuses any other count
+        off = np.zeros(n_reads + 1, np.int64)
+        rc = self._lib.chaindp_align_reads_debug_placed(self._ctx, n_reads, _ptr(off), None, 0)
+        if rc != ERR_CAPACITY:
+            self._check(rc)
+        placed = np.zeros(max(int(off[-1]), 1), REG_DTYPE)
+        self._check(self._lib.chaindp_align_reads_debug_placed(self._ctx, n_reads, _ptr(off), _ptr(placed), len(placed)))
+        return off, placed[:int(off[-1])]
+
+    def align_reads_rounds(self):
+        """The regions of every round of align1 the last align_reads made (test hook): int64[rounds]."""
+        n = np.zeros(1, np.int64)
+        self._check(self._lib.chaindp_align_reads_debug_rounds(self._ctx, _ptr(n), 1))
+        out = np.zeros(int(n[0]) + 1, np.int64)
+        self._check(self._lib.chaindp_align_reads_debug_rounds(self._ctx, _ptr(out), len(out)))
+        return out[1:]
+
+    def align_reads_ms(self):
+        """Device milliseconds of the last align_reads made while profiling was on (tuning hook): dict of rounds, inv, finish, gather."""
+        ms = (C.c_double * 4)()
+        self._check(self._lib.chaindp_align_reads_debug_ms(self._ctx, ms))
+        return dict(zip(("rounds", "inv", "finish", "gather"), (float(x) for x in ms)))
+
+    def align_reads_set_lds_cap(self, cap=0):
+        """Test hook: later align_reads calls rank lists of up to `cap` records in LDS and longer ones in global memory; 0: the built-in
+        cap, which is returned."""
+        out = np.zeros(1, np.int32)
+        self._check(self._lib.chaindp_align_reads_debug_set_lds_cap(self._ctx, int(cap), _ptr(out)))
+        return int(out[0])
 
     def align_inv_ll(self, n):
         """score, qe, te of ksw_ll_i16 for the n candidate pairs of the last align1_inv, on the reversed stretches (test hook): int32[n, 3]."""

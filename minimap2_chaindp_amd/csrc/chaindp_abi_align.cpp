@@ -30,9 +30,9 @@ extern "C" int chaindp_align_set_targets(chaindp_ctx_t *ctx, int64_t n_seqs, con
 	if ((rc = ksw_grow(ctx, ctx->al_tgt, (size_t)total * 2 + 16, "targets", "chaindp_align_set_targets"))) return rc;
 	if ((rc = ksw_grow(ctx, ctx->al_toff, (size_t)(n_seqs + 1) * sizeof(int64_t), "target offsets", "chaindp_align_set_targets"))) return rc;
 	hipStream_t st = ctx->stream;
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->al_toff.p, seq_off, (size_t)(n_seqs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, host_copy(ctx->al_toff.p, seq_off, (size_t)(n_seqs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
 	if (total) {
-		HIP_TRY(ctx, hipMemcpyAsync((char*)ctx->al_tgt.p + total, seq, (size_t)total, hipMemcpyHostToDevice, st));
+		HIP_TRY(ctx, host_copy((char*)ctx->al_tgt.p + total, seq, (size_t)total, hipMemcpyHostToDevice, st));
 		HIP_TRY(ctx, launch_align_encode(st, total, (const char*)ctx->al_tgt.p + total, (uint8_t*)ctx->al_tgt.p));
 	}
 	HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -72,16 +72,24 @@ extern "C" int chaindp_align1(chaindp_ctx_t *ctx, const chaindp_align_opt_t *opt
                               const int64_t *a_off, chaindp_anchor_t *a, const int64_t *regs_off, chaindp_reg_t *regs, chaindp_reg_t *regs2,
                               chaindp_align_extra_t *extra, int64_t *cigar_off, uint32_t *cigar, int64_t cigar_cap)
 {
+	return align1_impl(ctx, opt, n_reads, seq_off, seq, a_off, a, regs_off, regs, regs2, extra, cigar_off, cigar, cigar_cap, nullptr);
+}
+
+int chaindp::align1_impl(chaindp_ctx *ctx, const chaindp_align_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seq, const int64_t *a_off,
+                         chaindp_anchor_t *a, const int64_t *regs_off, chaindp_reg_t *regs, chaindp_reg_t *regs2, chaindp_align_extra_t *extra,
+                         int64_t *cigar_off, uint32_t *cigar, int64_t cigar_cap, AlignResident *res)
+{
 	if (!ctx) return CHAINDP_ERR_ARG;
 	if (!cigar_off) { ctx->err = "chaindp_align1: NULL cigar_off"; return CHAINDP_ERR_ARG; }
-	if (cigar_cap < 0 || (cigar_cap > 0 && !cigar)) { ctx->err = "chaindp_align1: cigar_cap without a cigar array"; return CHAINDP_ERR_ARG; }
-	AlignPlan ap;
+	if (!res && (cigar_cap < 0 || (cigar_cap > 0 && !cigar))) { ctx->err = "chaindp_align1: cigar_cap without a cigar array"; return CHAINDP_ERR_ARG; }
+	AlignPlan planned;
 	const int64_t n_t = (int64_t)ctx->al_t_off.size() - 1;
-	if (align_plan((const AlignOpt*)opt, n_reads, seq_off, a_off, (const uint64_t*)a, regs_off, (const int32_t*)regs, n_t < 0 ? 0 : n_t,
-	               n_t < 0 ? nullptr : ctx->al_t_off.data(), ap)) {
-		ctx->err = ap.err;
+	if (!(res && res->plan) && align_plan((const AlignOpt*)opt, n_reads, seq_off, a_off, (const uint64_t*)a, regs_off, (const int32_t*)regs, n_t < 0 ? 0 : n_t,
+	               n_t < 0 ? nullptr : ctx->al_t_off.data(), planned)) {
+		ctx->err = planned.err;
 		return CHAINDP_ERR_ARG;
 	}
+	const AlignPlan &ap = res && res->plan ? *res->plan : planned;
 	const AlignOpt o = *(const AlignOpt*)opt;
 	KswScore sc;
 	if (!ksw_plan_score(o.a, o.b, o.q, o.e, o.q2, o.e2, sc)) { ctx->err = "chaindp_align1: scoring"; return CHAINDP_ERR_ARG; }
@@ -89,16 +97,17 @@ extern "C" int chaindp_align1(chaindp_ctx_t *ctx, const chaindp_align_opt_t *opt
 	const int64_t G = ap.n_regs;
 	if (G == 0) return CHAINDP_OK;
 	if (!regs2 || !extra) { ctx->err = "chaindp_align1: NULL regs2 or extra"; return CHAINDP_ERR_ARG; }
-	if (ap.n_bases > 0 && !seq) { ctx->err = "chaindp_align1: NULL sequence"; return CHAINDP_ERR_ARG; }
+	if (ap.n_bases > 0 && !seq && !res) { ctx->err = "chaindp_align1: NULL sequence"; return CHAINDP_ERR_ARG; }
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // a buffer that grows is freed: nothing of an earlier call may be in flight
 	hipStream_t st = ctx->stream;
 	int rc;
 	// the batch: offsets, the regions' reads, anchors, regions, bases
 	Carve in;
-	const size_t o_seq_off = in.take((size_t)(n_reads + 1) * 8), o_a_off = in.take((size_t)(n_reads + 1) * 8), o_slot_off = in.take((size_t)(G + 1) * 8),
-	             o_first = in.take((size_t)(G + 1) * 8), o_reg_read = in.take((size_t)G * 4), o_a = in.take((size_t)ap.n_anchors * 16),
-	             o_regs = in.take((size_t)G * 80), o_regs2 = in.take((size_t)G * 80), o_seq = in.take((size_t)ap.n_bases);
+	// (the reads' own part is the caller's where the batch is resident)
+	const size_t o_seq_off = in.take(res ? 0 : (size_t)(n_reads + 1) * 8), o_a_off = in.take(res ? 0 : (size_t)(n_reads + 1) * 8), o_slot_off = in.take((size_t)(G + 1) * 8),
+	             o_first = in.take((size_t)(G + 1) * 8), o_reg_read = in.take((size_t)G * 4), o_a = in.take(res ? 0 : (size_t)ap.n_anchors * 16),
+	             o_regs = in.take((size_t)G * 80), o_regs2 = in.take((size_t)G * 80), o_seq = in.take(res ? 0 : (size_t)ap.n_bases);
 	if ((rc = ksw_grow(ctx, ctx->al_in, in.at + 16, "the batch", WHO))) return rc;
 	Carve rg;
 	const size_t o_areg = rg.take((size_t)G * sizeof(AlignReg)), o_stitch = rg.take((size_t)G * sizeof(AlignStitch)), o_extra = rg.take((size_t)G * 20),
@@ -115,27 +124,30 @@ extern "C" int chaindp_align1(chaindp_ctx_t *ctx, const chaindp_align_opt_t *opt
 	d.seq_off = (const int64_t*)(d_in + o_seq_off); d.a_off = (const int64_t*)(d_in + o_a_off); d.slot_off = (const int64_t*)(d_in + o_slot_off);
 	d.first = (const int64_t*)(d_in + o_first); d.reg_read = (const int32_t*)(d_in + o_reg_read); d.a = d_in + o_a;
 	d.regs = (int32_t*)(d_in + o_regs); d.regs2 = (int32_t*)(d_in + o_regs2); d.seq = d_in + o_seq;
+	if (res) { d.seq_off = res->seq_off; d.a_off = res->a_off; d.a = res->a; d.seq = res->seq; }
 	d.t_off = (const int64_t*)ctx->al_toff.p; d.tcodes = (const uint8_t*)ctx->al_tgt.p;
 	d.slots = (KswProb*)ctx->al_slot.p; d.side = (AlignSide*)((char*)ctx->al_side.p + o_side); d.kbuf = (int32_t*)((char*)ctx->al_side.p + o_kbuf);
 	d.areg = (AlignReg*)(d_rg + o_areg); d.stitch = (AlignStitch*)(d_rg + o_stitch); d.extra = (int32_t*)(d_rg + o_extra);
 	int64_t *d_coff = (int64_t*)(d_rg + o_coff);
-	auto up = [&](size_t off, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(d_in + off, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
-	HIP_TRY(ctx, up(o_seq_off, seq_off, (size_t)(n_reads + 1) * 8));
-	HIP_TRY(ctx, up(o_a_off, a_off, (size_t)(n_reads + 1) * 8));
+	auto up = [&](size_t off, const void *src, size_t bytes) { return bytes ? host_copy(d_in + off, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
+	if (!res) {
+		HIP_TRY(ctx, up(o_seq_off, seq_off, (size_t)(n_reads + 1) * 8));
+		HIP_TRY(ctx, up(o_a_off, a_off, (size_t)(n_reads + 1) * 8));
+		HIP_TRY(ctx, up(o_a, a, (size_t)ap.n_anchors * 16));
+		HIP_TRY(ctx, up(o_seq, seq, (size_t)ap.n_bases));
+	}
 	HIP_TRY(ctx, up(o_slot_off, ap.slot_off.data(), (size_t)(G + 1) * 8));
 	HIP_TRY(ctx, up(o_reg_read, ap.reg_read.data(), (size_t)G * 4));
-	HIP_TRY(ctx, up(o_a, a, (size_t)ap.n_anchors * 16));
 	HIP_TRY(ctx, up(o_regs, regs, (size_t)G * 80));
 	HIP_TRY(ctx, up(o_regs2, regs2, (size_t)G * 80));
-	HIP_TRY(ctx, up(o_seq, seq, (size_t)ap.n_bases));
 	StageEvents ev(ctx);
 	HIP_TRY(ctx, ev.mark(-1));
 	HIP_TRY(ctx, launch_align_plan(st, o, d));
 	HIP_TRY(ctx, ev.mark(0));
 	std::vector<AlignReg> areg((size_t)G);
 	std::vector<KswProb> slots(S);
-	HIP_TRY(ctx, hipMemcpyAsync(areg.data(), d.areg, (size_t)G * sizeof(AlignReg), hipMemcpyDeviceToHost, st));
-	if (S) HIP_TRY(ctx, hipMemcpyAsync(slots.data(), d.slots, S * sizeof(KswProb), hipMemcpyDeviceToHost, st));
+	HIP_TRY(ctx, host_copy(areg.data(), d.areg, (size_t)G * sizeof(AlignReg), hipMemcpyDeviceToHost, st));
+	if (S) HIP_TRY(ctx, host_copy(slots.data(), d.slots, S * sizeof(KswProb), hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipStreamSynchronize(st));
 	// the first pass: every extension and every fill of every region
 	KswPlan p1;
@@ -161,8 +173,8 @@ extern "C" int chaindp_align1(chaindp_ctx_t *ctx, const chaindp_align_opt_t *opt
 	std::vector<int32_t> sec(P, -1);
 	KswPlan p2;
 	if (P) {
-		HIP_TRY(ctx, hipMemcpyAsync(d_pc + o_prob, p1.prob.data(), P * sizeof(KswProb), hipMemcpyHostToDevice, st));
-		HIP_TRY(ctx, hipMemcpyAsync(d_pc + o_src, src_slot.data(), P * 4, hipMemcpyHostToDevice, st));
+		HIP_TRY(ctx, host_copy(d_pc + o_prob, p1.prob.data(), P * sizeof(KswProb), hipMemcpyHostToDevice, st));
+		HIP_TRY(ctx, host_copy(d_pc + o_src, src_slot.data(), P * 4, hipMemcpyHostToDevice, st));
 		HIP_TRY(ctx, ev.mark(-1));
 		HIP_TRY(ctx, launch_align_gather(st, d, (uint8_t*)ctx->ksw_bases.p));
 		HIP_TRY(ctx, ev.mark(0));
@@ -178,7 +190,7 @@ extern "C" int chaindp_align1(chaindp_ctx_t *ctx, const chaindp_align_opt_t *opt
 		HIP_TRY(ctx, hipMemcpyAsync(ctx->al_ez1.p, v1.ez, P * KSW_EZ_WORDS * 4, hipMemcpyDeviceToDevice, st));
 		if (p1.cig_words) HIP_TRY(ctx, hipMemcpyAsync(ctx->al_cig1.p, v1.cig, (size_t)p1.cig_words * 4, hipMemcpyDeviceToDevice, st));
 		std::vector<int32_t> code(P);
-		HIP_TRY(ctx, hipMemcpyAsync(code.data(), d.code, P * 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(ctx, host_copy(code.data(), d.code, P * 4, hipMemcpyDeviceToHost, st));
 		HIP_TRY(ctx, hipStreamSynchronize(st));
 		// the second pass: the fills whose code is not 0, without the approximate maximum, under the Z-drop the code names
 		p2.sc = sc;
@@ -189,7 +201,7 @@ extern "C" int chaindp_align1(chaindp_ctx_t *ctx, const chaindp_align_opt_t *opt
 			sec[c] = (int32_t)p2.prob.size();
 			p2.prob.push_back(p);
 		}
-		HIP_TRY(ctx, hipMemcpyAsync(d_pc + o_sec, sec.data(), P * 4, hipMemcpyHostToDevice, st));
+		HIP_TRY(ctx, host_copy(d_pc + o_sec, sec.data(), P * 4, hipMemcpyHostToDevice, st));
 		if (!p2.prob.empty()) {
 			ksw_plan_route(p2, ctx->dp.cus, ctx->ksw_grid_cap);
 			if ((rc = ksw_reserve(ctx, p2, n_bases, WHO))) return rc;
@@ -204,16 +216,18 @@ extern "C" int chaindp_align1(chaindp_ctx_t *ctx, const chaindp_align_opt_t *opt
 	HIP_TRY(ctx, ev.mark(3));
 	HIP_TRY(ctx, launch_align_extra(st, o, d));
 	HIP_TRY(ctx, ev.mark(4));
-	HIP_TRY(ctx, hipMemcpyAsync(extra, d.extra, (size_t)G * 20, hipMemcpyDeviceToHost, st));
-	HIP_TRY(ctx, hipMemcpyAsync(regs, d.regs, (size_t)G * 80, hipMemcpyDeviceToHost, st));
-	HIP_TRY(ctx, hipMemcpyAsync(regs2, d.regs2, (size_t)G * 80, hipMemcpyDeviceToHost, st));
-	if (ap.n_anchors) HIP_TRY(ctx, hipMemcpyAsync(a, d.a, (size_t)ap.n_anchors * 16, hipMemcpyDeviceToHost, st));
+	HIP_TRY(ctx, host_copy(extra, d.extra, (size_t)G * 20, hipMemcpyDeviceToHost, st));
+	HIP_TRY(ctx, host_copy(regs, d.regs, (size_t)G * 80, hipMemcpyDeviceToHost, st));
+	HIP_TRY(ctx, host_copy(regs2, d.regs2, (size_t)G * 80, hipMemcpyDeviceToHost, st));
+	if (ap.n_anchors && !res) HIP_TRY(ctx, host_copy(a, d.a, (size_t)ap.n_anchors * 16, hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipStreamSynchronize(st));
 	const int64_t total = cigar_prefix((const int32_t*)extra, 5, 4, G, cigar_off);
-	const int ret = cigar_pack_out(ctx, WHO, cigar_off, G, total, cigar, cigar_cap, d_coff, [&](uint32_t *out) {
+	const std::function<hipError_t(uint32_t*)> pack = [&](uint32_t *out) {
 		hipError_t e;
 		return (e = ev.mark(-1)) || (e = launch_align_pack(st, d, d_coff, out)) ? e : ev.mark(4);
-	});
+	};
+	if (res) { res->d_regs = d.regs; res->d_extra = d.extra; }
+	const int ret = res ? cigar_pack_dev(ctx, cigar_off, G, total, d_coff, res->room, pack) : cigar_pack_out(ctx, WHO, cigar_off, G, total, cigar, cigar_cap, d_coff, pack);
 	if (ret != CHAINDP_ERR_HIP && (rc = ev.fold(ctx->al_ms, 5))) return rc;
 	return ret;
 }

@@ -35,6 +35,13 @@ int chaindp::ksw_reserve(chaindp_ctx *ctx, const KswPlan &pl, int64_t n_bases, c
 	return CHAINDP_OK;
 }
 
+hipError_t chaindp::host_copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t st)
+{
+	for (size_t at = 0; at < bytes; at += KSW_COPY_PIECE)
+		if (hipError_t e = hipMemcpyAsync((char*)dst + at, (const char*)src + at, std::min(KSW_COPY_PIECE, bytes - at), kind, st)) return e;
+	return hipSuccess;
+}
+
 KswView chaindp::ksw_view(const chaindp_ctx *ctx, size_t N)
 {
 	const KswLayout lay(N);
@@ -71,8 +78,8 @@ int chaindp::ksw_dispatch(chaindp_ctx *ctx, const KswPlan &pl, StageEvents *ev)
 	const size_t N = pl.prob.size();
 	hipStream_t st = ctx->stream;
 	const KswView v = ksw_view(ctx, N);
-	HIP_TRY(ctx, hipMemcpyAsync(v.prob, pl.prob.data(), N * sizeof(KswProb), hipMemcpyHostToDevice, st));
-	HIP_TRY(ctx, hipMemcpyAsync(v.order, pl.order.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, host_copy(v.prob, pl.prob.data(), N * sizeof(KswProb), hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, host_copy(v.order, pl.order.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, st));
 	if (ev) HIP_TRY(ctx, ev->mark(-1));
 	// the wide problems first: theirs are the long workgroups, the one-wave ones fill in behind them
 	HIP_TRY(ctx, launch_ksw_extd(st, KSW_WIDE_WAVES, pl.grid[1], pl.lds_bytes[1], pl.count[1], v.prob, v.order + pl.count[0], (const uint8_t*)ctx->ksw_bases.p,
@@ -91,10 +98,22 @@ int chaindp::cigar_pack_out(chaindp_ctx *ctx, const char *who, const int64_t *ci
 	if (total == 0) return CHAINDP_OK;
 	hipStream_t st = ctx->stream;
 	if (int rc = ksw_grow(ctx, ctx->cigar_out, (size_t)total * sizeof(uint32_t) + 16, "CIGARs", who)) return rc;
-	HIP_TRY(ctx, hipMemcpyAsync(d_off, cigar_off, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, host_copy(d_off, cigar_off, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
 	HIP_TRY(ctx, launch((uint32_t*)ctx->cigar_out.p));
-	HIP_TRY(ctx, hipMemcpyAsync(cigar, ctx->cigar_out.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+	HIP_TRY(ctx, host_copy(cigar, ctx->cigar_out.p, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipStreamSynchronize(st));
+	return CHAINDP_OK;
+}
+
+int chaindp::cigar_pack_dev(chaindp_ctx *ctx, const int64_t *cigar_off, int64_t n, int64_t total, int64_t *d_off, const std::function<int(int64_t total, uint32_t **out)> &room,
+                            const std::function<hipError_t(uint32_t *out)> &launch)
+{
+	if (total == 0) return CHAINDP_OK;
+	uint32_t *out = nullptr;
+	if (int rc = room(total, &out)) return rc;
+	HIP_TRY(ctx, host_copy(d_off, cigar_off, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+	HIP_TRY(ctx, launch(out));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	return CHAINDP_OK;
 }
 
@@ -120,11 +139,11 @@ extern "C" int chaindp_ksw_extd(chaindp_ctx_t *ctx, int64_t n, const uint8_t *ba
 	if ((rc = ksw_reserve(ctx, pl, pl.n_bases, "chaindp_ksw_extd"))) return rc;
 	hipStream_t st = ctx->stream;
 	const KswView v = ksw_view(ctx, N);
-	if (pl.n_bases) HIP_TRY(ctx, hipMemcpyAsync(ctx->ksw_bases.p, bases, (size_t)pl.n_bases, hipMemcpyHostToDevice, st));
+	if (pl.n_bases) HIP_TRY(ctx, host_copy(ctx->ksw_bases.p, bases, (size_t)pl.n_bases, hipMemcpyHostToDevice, st));
 	StageEvents ev(ctx);                                 // the DP kernels' own time, apart from the copies around them
 	if ((rc = ksw_dispatch(ctx, pl, &ev))) return rc;
 	std::vector<int32_t> ez(N * KSW_EZ_WORDS);
-	HIP_TRY(ctx, hipMemcpyAsync(ez.data(), v.ez, ez.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+	HIP_TRY(ctx, host_copy(ez.data(), v.ez, ez.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipStreamSynchronize(st));
 	if ((rc = ev.fold(&ctx->ksw_ms, 1))) return rc;
 	ctx->ksw_n = n;
@@ -179,7 +198,7 @@ extern "C" int chaindp_ksw_debug_route(chaindp_ctx_t *ctx, int64_t n, int32_t *r
 	if (n == 0) return CHAINDP_OK;
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	std::vector<int32_t> ez((size_t)n * KSW_EZ_WORDS);
-	HIP_TRY(ctx, hipMemcpyAsync(ez.data(), ksw_view(ctx, (size_t)n).ez, ez.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, host_copy(ez.data(), ksw_view(ctx, (size_t)n).ez, ez.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 	for (int64_t i = 0; i < n; ++i) route[i] = ez[(size_t)i * KSW_EZ_WORDS + 11];
 	return CHAINDP_OK;

@@ -116,6 +116,20 @@ struct chaindp_ctx {
 	chaindp::DevGrow inv_in, inv_res, inv_ll;
 	int64_t inv_n = -1;                        // candidates of the last chaindp_align1_inv whose local scores are resident (chaindp_align_inv_debug_ll)
 	double inv_ms[4] = {-1, -1, -1, -1};       // local score, gather + DP, finish + skip, pack of the last call made while profiling was on
+	// mm_align_skeleton, chaindp_align_reads (allocated on first use, grown with the batch): the reads' offsets, bases and anchors for
+	// all rounds; the pool of records and the pool of CIGAR words the rounds and the inversion call leave (each one of a pair of
+	// buffers: a pool that grows moves to the other one, what it holds copied); the lists with the finish's work arrays; the result
+	chaindp::DevGrow rd_in, rd_rec[2], rd_cig[2], rd_list, rd_out, rd_out_cig;
+	int rd_rec_cur = 0, rd_cig_cur = 0;
+	int64_t rd_n_reads = -1;                   // reads of the resident result of the last chaindp_align_reads (-1: none)
+	int64_t rd_n_rec = 0;                      // records in its pool
+	int64_t rd_need[2] = {0, 0};               // its final regions and CIGAR words
+	size_t rd_out_at[5] = {0, 0, 0, 0, 0};     // where out_off, regs, extra, cigar_off lie in rd_out, and placed in rd_list
+	std::vector<int64_t> rd_rounds;            // regions per round of that call (chaindp_align_reads_debug_rounds)
+	std::vector<int64_t> rd_list_off;          // its lists: offsets and pool records, for chaindp_align_reads_debug_placed
+	std::vector<int32_t> rd_item;
+	int rd_lds_cap = RD_LDS_CAP;               // chaindp_align_reads_debug_set_lds_cap (tests): shorter lists stay in LDS
+	double rd_ms[4] = {-1, -1, -1, -1};        // rounds, inversions, finish, gather of the last call made while profiling was on
 	int frag_lds_cap = FRAG_LDS_CAP;           // chaindp_debug_set_frag_lds_cap (tests): fewer hits per fragment stay in LDS
 	// sketch (allocated on first use, grown with the batch)
 	chaindp::SketchArgs sk = {};
@@ -195,6 +209,11 @@ int post_finish(chaindp_ctx *ctx);
 // chaindp_abi_ksw.cpp: the host scaffold of the alignment stages (chaindp_ksw_extd, chaindp_align1, chaindp_align1_inv, and any new one)
 int ksw_grow(chaindp_ctx *ctx, DevGrow &g, size_t need, const char *what, const char *who);
 int ksw_reserve(chaindp_ctx *ctx, const KswPlan &pl, int64_t n_bases, const char *who);
+// Every copy of the alignment stages between host and device: in pieces of KSW_COPY_PIECE bytes, which the runtime moves through its own
+// staging buffers.  Given megabytes of pageable memory in one copy it pins the pages instead, and the pages of arrays that are
+// freed afterwards (a call's temporaries, a caller's outputs) cost a later synchronise 15 to 29 ms on an MI355X.
+#define KSW_COPY_PIECE ((size_t)256 << 10)
+hipError_t host_copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t st);
 // where the DP's records and results for N problems lie on the device (KswLayout over ksw_prob and ksw_ez), and its CIGAR staging
 struct KswView { KswProb *prob; int32_t *order; unsigned int *counter; int64_t *off; int32_t *ez; uint32_t *cig; };
 KswView ksw_view(const chaindp_ctx *ctx, size_t N);
@@ -216,7 +235,31 @@ int ksw_dispatch(chaindp_ctx *ctx, const KswPlan &pl, StageEvents *ev);
 int cigar_pack_out(chaindp_ctx *ctx, const char *who, const int64_t *cigar_off, int64_t n, int64_t total, uint32_t *cigar, int64_t cigar_cap,
                    int64_t *d_off, const std::function<hipError_t(uint32_t *out)> &launch);
 
+// The end of a call that leaves its CIGARs on the device: as cigar_pack_out, but launch(out) packs to the address room(total) names
+// (room returns 0 or the call's error code) and nothing comes down; the stream is idle afterwards.
+int cigar_pack_dev(chaindp_ctx *ctx, const int64_t *cigar_off, int64_t n, int64_t total, int64_t *d_off, const std::function<int(int64_t total, uint32_t **out)> &room,
+                   const std::function<hipError_t(uint32_t *out)> &launch);
+
 // ---- stage entry points that other stages call
+// A batch of an alignment stage whose reads are on the device already (chaindp_align_reads): the device addresses of seq_off, seq and,
+// for chaindp_align1, a_off and the anchors, which the stage then neither uploads nor, the anchors, downloads; where its packed
+// CIGARs go (total words in, a device address out; 0 or an error code).  The stage fills in where it left its per-region records on
+// the device: regs, extra (chaindp_align1) or r_inv, extra (chaindp_align1_inv), valid until the next call of that stage.
+struct AlignResident {
+	const int64_t *seq_off; const char *seq; const int64_t *a_off; void *a;
+	std::function<int(int64_t total, uint32_t **out)> room;
+	const AlignPlan *plan = nullptr;           // chaindp_align1 only: the caller has run align_plan on exactly these arguments already
+	const int32_t *d_regs = nullptr, *d_extra = nullptr;
+};
+// chaindp_align1 / chaindp_align1_inv with their arguments; res == nullptr: exactly the public call.  With res, seq and a are read only
+// by the planner (a may carry the marks of an earlier round or not: the planner reads none of a[].y's flag bits), cigar and cigar_cap
+// are ignored and cigar_off is still filled.
+int align1_impl(chaindp_ctx *ctx, const chaindp_align_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seq, const int64_t *a_off,
+                chaindp_anchor_t *a, const int64_t *regs_off, chaindp_reg_t *regs, chaindp_reg_t *regs2, chaindp_align_extra_t *extra, int64_t *cigar_off,
+                uint32_t *cigar, int64_t cigar_cap, AlignResident *res);
+int align1_inv_impl(chaindp_ctx *ctx, const chaindp_align_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seq, const int64_t *regs_off,
+                    const chaindp_reg_t *regs, int32_t *made, chaindp_reg_t *r_inv, chaindp_align_extra_t *extra, int64_t *cigar_off, uint32_t *cigar,
+                    int64_t cigar_cap, AlignResident *res);
 int collect_seeds_impl(chaindp_ctx *ctx, const chaindp_index_t *ix, int flag, int max_occ, int64_t n_reads,
                        const int64_t *mini_off, const chaindp_anchor_t *mini, const chaindp_anchor_t *const *read_mini,
                        const uint32_t *bid, const int32_t *qlen,

@@ -7,6 +7,7 @@
 #include "chaindp_ksw_plan.h"
 #include "chaindp_align_plan.h"
 #include "chaindp_inv_plan.h"
+#include "chaindp_reads_plan.h"
 
 namespace chaindp {
 
@@ -397,6 +398,23 @@ hipError_t launch_inv_gather(hipStream_t st, const InvDev &d, uint8_t *d_bases);
 hipError_t launch_inv_finish(hipStream_t st, const AlignOpt &o, const InvDev &d, const int32_t *d_ez, uint32_t *d_cig);
 hipError_t launch_inv_skip(hipStream_t st, const InvDev &d);
 hipError_t launch_inv_pack(hipStream_t st, const InvDev &d, const int64_t *d_off, const uint32_t *d_cig, uint32_t *d_out);
+
+// The end of mm_align_skeleton (align.c:758-759) over the pool of records chaindp_align_reads kept: reads/chaindp_reads.hip.  A pool
+// record is RD_REC_WORDS words (the region, then its chaindp_align_extra_t); the L listed records lie read by read (list_off) in pool
+// order, each with its place key and the place of its CIGAR words in the pool.  Everything below `work` is the kernels' own.
+struct ReadsDev {
+	int64_t n_reads, n_listed;
+	const int64_t *seq_off, *list_off; const int32_t *item; const unsigned long long *key; const int64_t *cig_at;
+	const int32_t *rec; const uint32_t *cig;
+	// work: the placed order and the final order as list indices, the global route's sort keys and marks, per read the final regions and words
+	int32_t *placed, *final_order; unsigned long long *sort_key; uint32_t *mark; int32_t *cnt; int64_t *words, *word_off; int32_t *src;
+	// the resident result: out_off[n_reads + 1], need[2], regs, extra, cigar_off[n_listed + 1], the CIGAR words
+	int64_t *out_off, *need; int32_t *out_regs, *out_extra; int64_t *cigar_off; uint32_t *out_cig;
+};
+hipError_t launch_reads_keep(hipStream_t st, int64_t n, const int32_t *d_regs, const int32_t *d_extra, int32_t *d_rec);
+// lds_cap: lists of up to so many records are ranked in LDS (at most RD_LDS_CAP), longer ones through sort_key and mark
+hipError_t launch_reads_finish(hipStream_t st, const AlignOpt &o, const ReadsDev &d, int lds_cap);
+hipError_t launch_reads_gather(hipStream_t st, const ReadsDev &d);
 
 } // namespace chaindp
 #endif
