@@ -432,4 +432,5 @@ int chaindp_set_variant(chaindp_ctx_t *ctx, int force_general);
 #include "chaindp_align.h"
 #include "chaindp_align_inv.h"
 #include "chaindp_align_reads.h"
+#include "chaindp_align_post.h"
 #endif

@@ -35,6 +35,8 @@ ALIGN_SYMBOLS = tuple(_cabi.prototypes("chaindp_align.h"))
 ALIGN_INV_SYMBOLS = tuple(_cabi.prototypes("chaindp_align_inv.h"))
 # ... and for mm_align_skeleton
 ALIGN_READS_SYMBOLS = tuple(_cabi.prototypes("chaindp_align_reads.h"))
+# ... and for the tail of align_regs and mm_set_mapq over aligned regions
+ALIGN_POST_SYMBOLS = tuple(_cabi.prototypes("chaindp_align_post.h"))
 ALIGN_EXTRA_DTYPE = np.dtype([(k, "<i4") for k in ("has_extra", "dp_score", "dp_max", "n_ambi", "n_cigar")])   # chaindp_align_extra_t
 ERR_CAPACITY = -2
 
@@ -51,7 +53,7 @@ _lib = None
 
 
 def lib():
-    """The library, every function of include/chaindp.h, chaindp_gaps.h, chaindp_ksw.h, chaindp_align.h, chaindp_align_inv.h, chaindp_align_reads.h and chaindp_debug.h bound with the
+    """The library, every function of include/chaindp.h, chaindp_gaps.h, chaindp_ksw.h, chaindp_align.h, chaindp_align_inv.h, chaindp_align_reads.h, chaindp_align_post.h and chaindp_debug.h bound with the
     header's prototype."""
     global _lib
     if _lib is None:
@@ -59,7 +61,7 @@ def lib():
             raise ChainDPError(f"{LIB_PATH} is missing: build it with __graft_entry__.build() "
                                "(make -C minimap2_chaindp_amd/csrc); there is no fallback path")
         _lib = _cabi.bind(C.CDLL(LIB_PATH), "chaindp.h", "chaindp_gaps.h", "chaindp_ksw.h", "chaindp_align.h", "chaindp_align_inv.h", "chaindp_align_reads.h",
-                          "chaindp_debug.h")
+                          "chaindp_align_post.h", "chaindp_debug.h")
     return _lib
 
 
@@ -71,6 +73,31 @@ def post_logf_patches():
     k, v = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.float32)
     L.chaindp_post_logf_patches(_ptr(k), _ptr(v), n)
     return k[:n], v[:n]
+
+
+def apost_logf_patches(match_sc):
+    """The host's patch list of logf((float)dp_max / match_sc) (needs no GPU): (dp_max uint32[n], value float32[n]) for the dp_max in
+    [1, 2^24] where the host's logf is not the float the device computes by itself (the correctly rounded (float)log((double)x), x the
+    float quotient), or where log(x) comes too close to a float rounding midpoint for that to be certain."""
+    L = lib()
+    n = int(L.chaindp_apost_logf_patches(int(match_sc), None, None, 0))
+    if n < 0:
+        raise ValueError("match_sc must be positive")
+    k, v = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.float32)
+    L.chaindp_apost_logf_patches(int(match_sc), _ptr(k), _ptr(v), n)
+    return k[:n], v[:n]
+
+
+def align_post_check(opt, rep_len, regs_off=None, regs=None, extra=None, cigar_off=None, cigar=None, regs_cap=0, cigar_cap=0):
+    """What Device.align_post makes of its arguments before anything touches the device (test hook, needs no GPU): (rc, regions,
+    CIGAR words handed in); rc is 0 or CHAINDP_ERR_ARG (-1)."""
+    rep_len = _arr(rep_len, np.int32)
+    regs_off, regs, extra = _arr(regs_off, np.int64), _arr(regs, REG_DTYPE), _arr(extra, ALIGN_EXTRA_DTYPE)
+    cigar_off, cigar = _arr(cigar_off, np.int64), _arr(cigar, np.uint32)
+    out = (C.c_int64 * 2)()
+    rc = lib().chaindp_align_post_debug_check(C.byref(opt) if opt is not None else None, len(rep_len), _ptr0(rep_len), _ptr(regs_off), _ptr0(regs), _ptr0(extra),
+                                              _ptr(cigar_off), _ptr0(cigar), int(regs_cap), int(cigar_cap), out)
+    return rc, int(out[0]), int(out[1])
 
 
 def device_count():
@@ -122,6 +149,12 @@ _CAPS = {
     # resident, so a guess that was short is made good by the fetch call, nothing is computed again
     "align_reads":       _Cap("n_regs2", 1, True, "raise", "align_reads_fetch", None),
     "align_reads_cigar": _Cap("n_bases", 4, True, "raise", "align_reads_fetch", None),
+    # align_post finishes regions that are on the device or come from the host: nothing is added, so the regions and words handed in are
+    # room enough; for the resident result of align_reads the host knows neither count, guesses, and fetches what was short
+    "align_post":        _Cap("n_regs",  1, True, "raise", "align_post_fetch", None),
+    "align_post_cigar":  _Cap("n_words", 1, True, "raise", "align_post_fetch", None),
+    "align_reads_post":       _Cap("n_regs2", 1, True, "raise", "align_post_fetch", None),
+    "align_reads_post_cigar": _Cap("n_bases", 4, True, "raise", "align_post_fetch", None),
     "ksw_extd":      _Cap("n_span",  1,  False, "raise", None,         None),      # room for q_len + t_len words a problem: never short
 }
 
@@ -682,6 +715,105 @@ class Device:
         self._check(rc)
         n, m = int(need[0]), int(need[1])
         return a_out, out_off, o[0][:n], o[1][:n], o[2][:n + 1], o[3][:m]
+
+    # -- aligned reads finished: the tail of align_regs and mm_set_mapq (chaindp_align_post and its siblings)
+    def _finished(self, rows, given, size, n_reads, call, attach):
+        """The room logic of the calls that return finished regions, by their two rows of _CAPS (regions, CIGAR words), as _cigars does it
+        for one kind of room: call(*room) -> rc with room = (out_off, regs, extra, dp_max2, regs_cap, cigar_off, cigar, cigar_cap, need).
+        A guess that was short is made good by the rows' fetch call; a cap of the caller's that is short raises ChainDPError with
+        `attach` and regs_off, need attached.  Returns (regs_off, regs, extra, dp_max2, cigar_off, cigar)."""
+        rows = [_CAPS[r] for r in rows]
+        caps = [int(c) if c is not None else max(size[row.source] // row.divisor, REGS_CAP_FLOOR if row.floored else 1) for c, row in zip(given, rows)]
+        out_off, need = np.zeros(n_reads + 1, np.int64), np.zeros(2, np.int64)
+
+        def outputs():
+            return (np.zeros(max(caps[0], 1), REG_DTYPE), np.zeros(max(caps[0], 1), ALIGN_EXTRA_DTYPE), np.zeros(max(caps[0], 1), np.int32),
+                    np.zeros(max(caps[0], 0) + 1, np.int64), np.zeros(max(caps[1], 1), np.uint32))
+
+        def room(o):
+            return _ptr(out_off), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), caps[0], _ptr(o[3]), _ptr(o[4]), caps[1], _ptr(need)
+        o = outputs()
+        rc = call(*room(o))
+        short = rc == ERR_CAPACITY and (int(need[0]) > caps[0] or int(need[1]) > caps[1])   # else out of device memory, or a logf argument
+        if short:
+            if any(c is not None and int(n) > cap for c, n, cap in zip(given, need, caps)):
+                err = ChainDPError(f"chaindp error {rc}: {self._lib.chaindp_last_error(self._ctx).decode()}")
+                err.__dict__.update(attach, regs_off=out_off, need=need)
+                raise err
+            caps = [max(cap, int(n)) for cap, n in zip(caps, need)]
+            o = outputs()
+            rc = getattr(self._lib, "chaindp_" + rows[0].retry)(self._ctx, n_reads, *room(o))
+        self._check(rc)
+        n, m = int(need[0]), int(need[1])
+        return out_off, o[0][:n], o[1][:n], o[2][:n], o[3][:n + 1], o[4][:m]
+
+    def align_post(self, opt, rep_len, regs_off=None, regs=None, extra=None, cigar_off=None, cigar=None, regs_cap=None, cigar_cap=None):
+        """What the reference does with aligned regions before it prints them (chaindp_align_post / chaindp_align_post_regs): mm_set_parent
+        with r->p, mm_select_sub, mm_set_sam_pri (unless MM_F_ALL_CHAINS), then mm_set_mapq with mm_set_inv_mapq.  opt: params.PostOpt;
+        rep_len int32[n_reads].  regs_off None: on the resident result of the last align_reads, which stays valid; else on the regions
+        given, in the form align_reads returns them (a region with has_extra == 0 takes the r->p == NULL branches).  Returns (regs_off
+        int64[n_reads + 1], regs REG_DTYPE[...], extra ALIGN_EXTRA_DTYPE[...], dp_max2 int32[...], cigar_off int64[len(regs) + 1], cigar
+        uint32[...]).  regs_cap / cigar_cap as in align_reads; a short cap of the caller's raises with err.regs_off / .need."""
+        rep_len = _arr(rep_len, np.int32)
+        n_reads = len(rep_len)
+        if regs_off is None:
+            if any(x is not None for x in (regs, extra, cigar_off, cigar)):
+                raise ValueError("regs, extra, cigar_off and cigar go with regs_off")
+            size = dict(n_regs=0, n_words=0)
+
+            def call(*room):
+                return self._lib.chaindp_align_post(self._ctx, C.byref(opt), n_reads, _ptr0(rep_len), *room)
+        else:
+            regs_off, regs_in, extra_in = _arr(regs_off, np.int64), _arr(regs, REG_DTYPE), _arr(extra, ALIGN_EXTRA_DTYPE)
+            coff, cig = _arr(cigar_off, np.int64), _arr(cigar, np.uint32)
+            if len(regs_off) != n_reads + 1 or len(extra_in) != len(regs_in) or len(coff) != len(regs_in) + 1:
+                raise ValueError("regs_off needs one entry per read and one more, extra one per region, cigar_off one per region and one more")
+            size = dict(n_regs=len(regs_in), n_words=len(cig))
+
+            def call(*room):
+                return self._lib.chaindp_align_post_regs(self._ctx, C.byref(opt), n_reads, _ptr0(rep_len), _ptr(regs_off), _ptr0(regs_in), _ptr0(extra_in),
+                                                         _ptr(coff), _ptr0(cig), *room)
+        return self._finished(("align_post", "align_post_cigar"), (regs_cap, cigar_cap), size, n_reads, call, {})
+
+    def align_reads_post(self, aopt, opt, seq_off, seq, a_off, a, regs_off, regs, rep_len, regs_cap=None, cigar_cap=None):
+        """align_reads and align_post in one call (chaindp_align_reads_post): only the finished result comes down.  Returns (a, regs_off,
+        regs, extra, dp_max2, cigar_off, cigar); both results are resident afterwards."""
+        (seq, seq_off), a_off, regs_off = self._seqs(seq, seq_off), _arr(a_off, np.int64), _arr(regs_off, np.int64)
+        a_out, regs_in, rep_len = _arr(a, np.uint64).reshape(-1, 2).copy(), _arr(regs, REG_DTYPE), _arr(rep_len, np.int32)
+        n_reads, n_regs = len(seq_off) - 1, len(regs_in)
+        if len(a_off) != n_reads + 1 or len(regs_off) != n_reads + 1 or int(a_off[-1]) != len(a_out) or int(regs_off[-1]) != n_regs or int(seq_off[-1]) != len(seq) \
+                or len(rep_len) != n_reads:
+            raise ValueError("seq_off, a_off and regs_off need one entry per read and one more, rep_len one per read, and the offsets must end at the sizes of seq, a and regs")
+
+        def call(*room):
+            rc = self._lib.chaindp_align_reads_post(self._ctx, C.byref(aopt), C.byref(opt), n_reads, _ptr(seq_off), _ptr0(seq), _ptr(a_off), _ptr0(a_out),
+                                                    _ptr(regs_off), _ptr0(regs_in), _ptr0(rep_len), *room)
+            if rc in (0, ERR_CAPACITY):
+                self._align_reads_n = n_reads
+            return rc
+        return (a_out, *self._finished(("align_reads_post", "align_reads_post_cigar"), (regs_cap, cigar_cap), dict(n_regs2=2 * n_regs, n_bases=len(seq)), n_reads,
+                                       call, dict(a=a_out)))
+
+    def align_post_ms(self):
+        """Device milliseconds of the last align_post / align_reads_post made while profiling was on (tuning hook): dict of read (the one
+        kernel of the tail and mapq, with the scans) and gather."""
+        ms = (C.c_double * 2)()
+        self._check(self._lib.chaindp_align_post_debug_ms(self._ctx, ms))
+        return dict(zip(("read", "gather"), (float(x) for x in ms)))
+
+    def align_post_set_lds_cap(self, cap=0):
+        """Test hook: later align_post calls stage lists of up to `cap` regions in LDS and longer ones in global memory; 0: the built-in
+        cap, which is returned."""
+        out = np.zeros(1, np.int32)
+        self._check(self._lib.chaindp_align_post_debug_set_lds_cap(self._ctx, int(cap), _ptr(out)))
+        return int(out[0])
+
+    def apost_logf_selftest(self, match_sc, kmax=1 << 24):
+        """The number of dp_max in [1, kmax] where the device's logf((float)dp_max / match_sc) differs from the host's (test hook)."""
+        n = int(self._lib.chaindp_apost_logf_selftest(self._ctx, int(match_sc), int(kmax)))
+        if n < 0:
+            self._check(n)
+        return n
 
     def align_reads_placed(self):
         """Each read's list of the last align_reads as it stood ahead of mm_filter_regs, split-off regions and inversions in their places

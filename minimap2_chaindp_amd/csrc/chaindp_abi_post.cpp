@@ -35,7 +35,7 @@ extern "C" int64_t chaindp_post_logf_patches(uint32_t *k, float *v, int64_t cap)
 	return n;
 }
 
-static int post_logf_upload(chaindp_ctx *ctx)
+int chaindp::post_logf_upload(chaindp_ctx *ctx)
 {
 	if (ctx->logf_ready) return CHAINDP_OK;
 	build_logf_patches();

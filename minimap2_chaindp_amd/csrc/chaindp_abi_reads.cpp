@@ -4,6 +4,8 @@
 // file owns the loop's buffers, the two pools that outlive a round, the copies and the order of the calls:
 //   bases, anchors up -> round 0, 1, ... (each: records into the pool, CIGARs packed into the pool, regs2 down) -> inversions over the
 //   lists (the same) -> anchors down -> lists up -> finish -> gather -> (need, out_off down) -> the result down, or later by fetch
+// align_reads_compute is everything up to the resident result (chaindp_align_reads_post runs the post stage on it before anything comes
+// down); deliver brings a resident result into the caller's arrays.
 #include "chaindp_ctx.h"
 #include "../../include/chaindp_align_reads.h"
 #include <string.h>
@@ -140,6 +142,13 @@ extern "C" int chaindp_align_reads(chaindp_ctx_t *ctx, const chaindp_align_opt_t
 {
 	if (!ctx) return CHAINDP_ERR_ARG;
 	if (int rc = check_outputs(ctx, WHO, out_off, out_regs, out_extra, regs_cap, cigar_off, cigar, cigar_cap, need)) return rc;
+	if (int rc = align_reads_compute(ctx, opt, n_reads, seq_off, seq, a_off, a, regs_off, regs, regs_cap, cigar_cap)) return rc;
+	return deliver(ctx, WHO, n_reads, out_off, out_regs, out_extra, regs_cap, cigar_off, cigar, cigar_cap, need);
+}
+
+int chaindp::align_reads_compute(chaindp_ctx *ctx, const chaindp_align_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seq, const int64_t *a_off,
+                                 chaindp_anchor_t *a, const int64_t *regs_off, const chaindp_reg_t *regs, int64_t regs_cap, int64_t cigar_cap)
+{
 	const int64_t n_t = (int64_t)ctx->al_t_off.size() - 1;
 	AlignPlan plan0;
 	if (reads_check((const AlignOpt*)opt, n_reads, seq_off, a_off, (const uint64_t*)a, regs_off, (const int32_t*)regs, n_t < 0 ? 0 : n_t,
@@ -152,7 +161,7 @@ extern "C" int chaindp_align_reads(chaindp_ctx_t *ctx, const chaindp_align_opt_t
 	ctx->rd_rounds.clear(); ctx->rd_list_off.clear(); ctx->rd_item.clear();
 	if (n_reads == 0) {
 		ctx->rd_n_reads = 0;
-		return deliver(ctx, WHO, 0, out_off, out_regs, out_extra, regs_cap, cigar_off, cigar, cigar_cap, need);
+		return CHAINDP_OK;
 	}
 	const int64_t n_bases = seq_off[n_reads], n_a = a_off[n_reads];
 	if (n_bases > 0 && !seq) { ctx->err = "chaindp_align_reads: NULL sequence"; return CHAINDP_ERR_ARG; }
@@ -280,5 +289,5 @@ extern "C" int chaindp_align_reads(chaindp_ctx_t *ctx, const chaindp_align_opt_t
 	ctx->rd_rounds = pl.rounds;
 	ctx->rd_n_rec = (int64_t)pl.rec.size();
 	ctx->rd_n_reads = n_reads;
-	return deliver(ctx, WHO, n_reads, out_off, out_regs, out_extra, regs_cap, cigar_off, cigar, cigar_cap, need);
+	return CHAINDP_OK;
 }

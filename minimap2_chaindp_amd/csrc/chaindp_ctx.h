@@ -12,6 +12,7 @@
 #include "../../include/chaindp_debug.h"
 #include "chaindp_kernels.h"
 #include "chaindp_devmem.h"
+#include "chaindp_apost_plan.h"
 
 struct EventSet { hipEvent_t e[3]; int n; int slot0; };  // e[0..n): consecutive kernel boundaries; slot0 = first ms[] index
 
@@ -130,6 +131,15 @@ struct chaindp_ctx {
 	std::vector<int32_t> rd_item;
 	int rd_lds_cap = RD_LDS_CAP;               // chaindp_align_reads_debug_set_lds_cap (tests): shorter lists stay in LDS
 	double rd_ms[4] = {-1, -1, -1, -1};        // rounds, inversions, finish, gather of the last call made while profiling was on
+	// the tail of align_regs and mm_set_mapq, chaindp_align_post (allocated on first use, grown with the batch): what comes up from the
+	// host; the kernels' work arrays, with out_off; the result; its CIGAR words; the logf list of one match_sc
+	chaindp::DevGrow ap_in, ap_work, ap_out, ap_out_cig, ap_dp;
+	int64_t ap_n_reads = -1;                   // reads of the resident result of the last chaindp_align_post (-1: none)
+	int64_t ap_need[2] = {0, 0};               // its final regions and CIGAR words
+	size_t ap_at[5] = {0, 0, 0, 0, 0};         // where out_off lies in ap_work and regs, extra, dp_max2, cigar_off in ap_out
+	int ap_dp_sc = 0, ap_n_dp = 0;             // the match_sc whose list ap_dp holds (0: none) and its entries
+	int ap_lds_cap = AP_LDS_CAP;               // chaindp_align_post_debug_set_lds_cap (tests): shorter lists stay in LDS
+	double ap_ms[2] = {-1, -1};                // k_apost_read with the scans, the gathers of the last call made while profiling was on
 	int frag_lds_cap = FRAG_LDS_CAP;           // chaindp_debug_set_frag_lds_cap (tests): fewer hits per fragment stay in LDS
 	// sketch (allocated on first use, grown with the batch)
 	chaindp::SketchArgs sk = {};
@@ -205,6 +215,7 @@ PostOpt to_post_opt(const chaindp_post_opt_t *o);
 int post_require_hits(chaindp_ctx *ctx, const char *who);
 int post_stage_rep_len(chaindp_ctx *ctx, const int32_t *rep_len, int64_t R, const int32_t **d_rep);
 int post_finish(chaindp_ctx *ctx);
+int post_logf_upload(chaindp_ctx *ctx);           // post_logf_int's list on the device: d_logf_k, d_logf_v, n_logf
 
 // chaindp_abi_ksw.cpp: the host scaffold of the alignment stages (chaindp_ksw_extd, chaindp_align1, chaindp_align1_inv, and any new one)
 int ksw_grow(chaindp_ctx *ctx, DevGrow &g, size_t need, const char *what, const char *who);
@@ -260,6 +271,9 @@ int align1_impl(chaindp_ctx *ctx, const chaindp_align_opt_t *opt, int64_t n_read
 int align1_inv_impl(chaindp_ctx *ctx, const chaindp_align_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seq, const int64_t *regs_off,
                     const chaindp_reg_t *regs, int32_t *made, chaindp_reg_t *r_inv, chaindp_align_extra_t *extra, int64_t *cigar_off, uint32_t *cigar,
                     int64_t cigar_cap, AlignResident *res);
+// chaindp_align_reads up to its resident result (chaindp_abi_reads.cpp): everything but the delivery into the caller's arrays
+int align_reads_compute(chaindp_ctx *ctx, const chaindp_align_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seq, const int64_t *a_off,
+                        chaindp_anchor_t *a, const int64_t *regs_off, const chaindp_reg_t *regs, int64_t regs_cap, int64_t cigar_cap);
 int collect_seeds_impl(chaindp_ctx *ctx, const chaindp_index_t *ix, int flag, int max_occ, int64_t n_reads,
                        const int64_t *mini_off, const chaindp_anchor_t *mini, const chaindp_anchor_t *const *read_mini,
                        const uint32_t *bid, const int32_t *qlen,

@@ -416,5 +416,26 @@ hipError_t launch_reads_keep(hipStream_t st, int64_t n, const int32_t *d_regs, c
 hipError_t launch_reads_finish(hipStream_t st, const AlignOpt &o, const ReadsDev &d, int lds_cap);
 hipError_t launch_reads_gather(hipStream_t st, const ReadsDev &d);
 
+// The tail of align_regs (map.c:253-257) and mm_set_mapq (map.c:876) over regions that carry alignments: apost/chaindp_apost.hip.  The
+// regions lie read by read (regs_off) with their chaindp_align_extra_t and the CSR of their CIGAR words; the sizes of the pieces are
+// chaindp_apost_plan.h's.  Everything below `work` is the kernels' own.
+struct ApostDev {
+	int64_t n_reads, n_regs;
+	const int64_t *regs_off; const int32_t *regs, *extra; const int64_t *cigar_off; const uint32_t *cig; const int32_t *rep_len;
+	const uint32_t *logf_k; const float *logf_v; int n_logf;        // post_logf_int's list
+	const uint32_t *dp_k; const float *dp_v; int n_dp;               // the list of the call's match_sc (apost_logf_build)
+	// work: per read the survivors and their CIGAR words (scanned in place: out_off, word_off), the survivors' records at their read's
+	// input places with dp_max2, the index within the read and the words before it within the read; the source of every final region;
+	// the global route's fields; the error word
+	unsigned long long *cnt, *words, *tile; int32_t *st_regs, *st_dp2, *st_src, *st_wpre; int64_t *fsrc; int32_t *scratch, *err;
+	// the resident result: out_off is cnt; need[2], regs, extra, dp_max2, cigar_off[n_regs + 1], the CIGAR words
+	int64_t *need; int32_t *out_regs, *out_extra, *out_dp2; int64_t *out_cigar_off; uint32_t *out_cig;
+};
+// lds_cap: lists of up to so many regions are staged in LDS (at most AP_LDS_CAP), longer ones in scratch
+hipError_t launch_apost_read(hipStream_t st, const PostOpt &o, const ApostDev &d, int lds_cap);
+hipError_t launch_apost_gather(hipStream_t st, const ApostDev &d);
+// out[k - 1] = the device's logf((float)k / match_sc) for k in [1, kmax]
+hipError_t launch_apost_logf_probe(hipStream_t st, int kmax, int match_sc, const uint32_t *d_k, const float *d_v, int n, float *d_out);
+
 } // namespace chaindp
 #endif

@@ -94,36 +94,6 @@ __global__ __launch_bounds__(256) void k_post_scatter(int64_t n_reads, const int
 	for (int64_t t = lane; t < words; t += 64) dst[t] = src[t];
 }
 
-// logf of an integer as the host computes it: the correctly rounded (float)log((double)k) -- log(k) stays more than 5 double ulp away
-// from every float rounding midpoint for k <= 2^24 -- except at the integers the host lists, where its logf rounds the other way
-__device__ __forceinline__ float post_logf_int(int k, const uint32_t *__restrict__ pk, const float *__restrict__ pv, int n_patch)
-{
-	const float c = (float)log((double)k);
-	if (k < 1 || k > POST_LOGF_MAX) return c;
-	int lo = 0, hi = n_patch - 1;
-	while (lo <= hi) {
-		const int mid = (lo + hi) >> 1;
-		const uint32_t m = pk[mid];
-		if (m == (uint32_t)k) return pv[mid];
-		if (m < (uint32_t)k) lo = mid + 1; else hi = mid - 1;
-	}
-	return c;
-}
-
-// (int)f as the reference's x86-64 build converts it (cvttss2si): INT_MIN for NaN and for anything outside the int range
-__device__ __forceinline__ int post_f2i(float f)
-{
-	if (!(f > -2147483904.0f && f < 2147483648.0f)) return INT_MIN;
-	return (int)f;
-}
-
-// (int)(4.343f * logf(n_sub + 1) + .499f) of hit.c:474: a float add of .499f (for n_sub + 1 <= 2^24 a double add differs from it at 119
-// integers, the first 141 265 -- beyond what a fixture reaches; chaindp_post_logf_selftest checks this term over the whole range)
-__device__ __forceinline__ int post_nsub_term(int k, const uint32_t *__restrict__ pk, const float *__restrict__ pv, int n_patch)
-{
-	return post_f2i(4.343f * post_logf_int(k, pk, pv, n_patch) + .499f);
-}
-
 // mm_set_mapq (hit.c:437-480) with r->p == NULL; mm_set_inv_mapq is a no-op here (no hit has its inv bit without alignment, and
 // the inv branch is kept for completeness).  err: set when a logf argument lies beyond the patch list.
 __global__ __launch_bounds__(256) void k_post_mapq(int64_t n_reads, const unsigned long long *__restrict__ out_off, const int32_t *__restrict__ rep_len,
