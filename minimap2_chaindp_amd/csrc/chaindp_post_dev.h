@@ -315,7 +315,8 @@ __device__ __forceinline__ int post_f2i(float f)
 }
 
 // (int)(4.343f * logf(n_sub + 1) + .499f) of hit.c:474: a float add of .499f (for n_sub + 1 <= 2^24 a double add differs from it at 119
-// integers, the first 141 265 -- beyond what a fixture reaches; chaindp_post_logf_selftest checks this term over the whole range)
+// integers, the first 141 265 -- reached through r[0].n_sub, which mm_set_parent never resets: the nsub_term scene of the align-post
+// edge tier sits on it; chaindp_post_logf_selftest checks this term over the whole range)
 __device__ __forceinline__ int post_nsub_term(int k, const uint32_t *__restrict__ pk, const float *__restrict__ pv, int n_patch)
 {
 	return post_f2i(4.343f * post_logf_int(k, pk, pv, n_patch) + .499f);

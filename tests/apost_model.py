@@ -20,6 +20,12 @@ COVER = ("read_without_regions", "one_region", "identical_after_dp", "dp_max2_se
          "mapq_dp2_alt_lower", "mapq_dp2_alt_higher", "mapq_dp2_is_sr", "mapq_p_dp2_zero", "mapq_no_p", "mapq_zero_to_one", "mapq_clamped_60",
          "mapq_negative", "mapq_float_outside_int", "inv_mapq_fewer_than_3", "inv_mapq_no_inversion", "inv_between_primaries", "inv_first_in_order",
          "inv_last_in_order", "list_over_64", "primaries_over_64")
+# the classes of the edge tier (tests/apost_edge_shapes.py), counted like COVER
+EDGE_COVER = ("overlaps_over_64", "found_at_rank_0_of_over_64", "found_at_rank_63", "found_at_rank_64", "none_found_of_over_64", "union_equal_start",
+              "mask_equals_level", "sum_sc_over_int32", "sum_sc_over_2p24", "nsub_float_add_decides", "mapq_wraps_to_60", "dp_max_not_positive_with_p",
+              "score_not_positive_without_p", "score0_zero", "identity_nan", "sub_dp_max_above_parent", "sub_above_parent_by_dp_only", "mapq_alt_negative",
+              "inv_at_rank_63", "inv_at_rank_64", "inv_index_decides", "inv_is_secondary", "inv_as_top_bit", "aux_parent_unset", "cigar_64_words",
+              "cigar_65_words", "cigar_none_beside_some", "final_over_64")
 SRC_DTYPE = np.dtype(REG_DTYPE.descr + [("src", "<i4")])
 
 cover = collections.Counter()
@@ -51,7 +57,12 @@ def set_parent(r, has_p, dp_max, dp_max2, mask_level, sub_diff):
             cov.append((max(sj, si), min(ej, ei)))
         found = -1
         if cov:
+            if len(cov) > 64:
+                cover["overlaps_over_64"] += 1
+            if len(set(s for s, _ in cov)) < len(cov):
+                cover["union_equal_start"] += 1
             cov.sort()
+            rank = -1
             x, uncov = si, 0
             for s, e in cov:
                 if s > x:
@@ -65,9 +76,19 @@ def set_parent(r, has_p, dp_max, dp_max2, mask_level, sub_diff):
                     continue
                 mn, mx = min(ej - sj, ei - si), max(ej - sj, ei - si)
                 ol_ = (0 if ei < sj else ei - sj if ei < ej else ej - sj) if si < sj else (0 if ej < si else ej - si if ej < ei else ei - si)
-                if F32(ol_) / F32(mn) - F32(uncov) / F32(mx) > ml:
+                rank += 1
+                val = F32(ol_) / F32(mn) - F32(uncov) / F32(mx)
+                if val == ml:
+                    cover["mask_equals_level"] += 1
+                if val > ml:
                     found = p
+                    if rank in (63, 64):
+                        cover["found_at_rank_%d" % rank] += 1
+                    elif rank == 0 and len(cov) > 64:
+                        cover["found_at_rank_0_of_over_64"] += 1
                     break
+            if found < 0 and len(cov) > 64:
+                cover["none_found_of_over_64"] += 1
         if found >= 0:
             rp = r[found]
             r[i]["parent"] = rp["parent"]
@@ -77,6 +98,10 @@ def set_parent(r, has_p, dp_max, dp_max2, mask_level, sub_diff):
                 if rp["rid"] != r[i]["rid"] or rp["rs"] != r[i]["rs"] or rp["re"] != r[i]["re"] or ol_ != mn:
                     dp_max2[found] = max(int(dp_max2[found]), int(dp_max[i]))
                     cover["dp_max2_set"] += 1
+                    if dp_max[i] > dp_max[found]:
+                        cover["sub_dp_max_above_parent"] += 1
+                        if not cnt_sub:
+                            cover["sub_above_parent_by_dp_only"] += 1
                     diff = _wrap32(int(dp_max[found]) - int(dp_max[i]))
                     if diff <= sub_diff:
                         if diff == sub_diff and not cnt_sub:
@@ -149,6 +174,8 @@ def set_mapq(r, has_p, dp_max, dp_max2, min_chain_sc, match_sc, rep_len, is_sr):
     n = len(r)
     sum_sc = int(sum(int(x["score"]) for x in r if x["parent"] == x["id"]))
     uniq_ratio = F32(sum_sc) / F32(sum_sc + rep_len)
+    if sum_sc > 1 << 24:
+        cover["sum_sc_over_int32" if sum_sc >= 1 << 31 else "sum_sc_over_2p24"] += 1
     q_coef = F32(40.0)
     for i, x in enumerate(r):
         bits = int(x["bits"])
@@ -167,6 +194,8 @@ def set_mapq(r, has_p, dp_max, dp_max2, min_chain_sc, match_sc, rep_len, is_sr):
                 mapq = _cvtt(identity * pen_cm * q_coef * (F32(1.0) - xx * xx) * logf_dp(dm, match_sc))
                 if not is_sr:
                     alt = _cvtt(F32(6.02) * identity * identity * F32(dm - d2) / F32(match_sc) + F32(.499))
+                    if alt < 0:
+                        cover["mapq_alt_negative"] += 1
                     cover["mapq_dp2_alt_lower" if alt < mapq else "mapq_dp2_alt_higher"] += 1
                     mapq = mapq if mapq < alt else alt
                 else:
@@ -182,7 +211,20 @@ def set_mapq(r, has_p, dp_max, dp_max2, min_chain_sc, match_sc, rep_len, is_sr):
                     cover["mapq_no_p"] += 1
             if mapq == INT_MIN:
                 cover["mapq_float_outside_int"] += 1
-            sub = _cvtt(F32(4.343) * host_logf(int(x["n_sub"]) + 1) + F32(.499))
+            if p and dm <= 0:
+                cover["dp_max_not_positive_with_p"] += 1
+            if not p and score <= 0:
+                cover["score_not_positive_without_p"] += 1
+            if int(x["score0"]) == 0:
+                cover["score0_zero"] += 1
+            if p and int(x["mlen"]) == 0 and int(x["blen"]) == 0:
+                cover["identity_nan"] += 1
+            lg_sub = F32(4.343) * host_logf(int(x["n_sub"]) + 1)
+            sub = _cvtt(lg_sub + F32(.499))
+            if int(np.float64(lg_sub) + np.float64(np.float32(.499))) != sub:
+                cover["nsub_float_add_decides"] += 1
+            if mapq == INT_MIN and sub > 0:
+                cover["mapq_wraps_to_60"] += 1
             mapq = _wrap32(mapq - sub)
             if mapq < 0 and mapq != _wrap32(INT_MIN - sub):
                 cover["mapq_negative"] += 1
@@ -203,8 +245,18 @@ def set_mapq(r, has_p, dp_max, dp_max2, min_chain_sc, match_sc, rep_len, is_sr):
         cover["inv_mapq_no_inversion"] += 1
         return
     aux = sorted((int(np.uint32(r[i]["as"])) << 32 | i) for i in range(n) if r[i]["parent"] == i or r[i]["parent"] < 0)
+    if any(int(x["bits"]) & BIT_INV and x["parent"] != x["id"] and x["parent"] >= 0 for x in r):
+        cover["inv_is_secondary"] += 1
+    if any(r[i]["parent"] < 0 and r[i]["id"] != r[i]["parent"] for i in range(n)):
+        cover["aux_parent_unset"] += 1
+    if any(r[i]["as"] < 0 for i in range(n) if r[i]["parent"] == i):
+        cover["inv_as_top_bit"] += 1
     for j, key in enumerate(aux):
         if int(r[key & 0xffffffff]["bits"]) & BIT_INV:
+            if j in (63, 64) and j < len(aux) - 1:
+                cover["inv_at_rank_%d" % j] += 1
+            if (j > 0 and aux[j - 1] >> 32 == key >> 32) or (j < len(aux) - 1 and aux[j + 1] >> 32 == key >> 32):
+                cover["inv_index_decides"] += 1
             cover["inv_first_in_order" if j == 0 else "inv_last_in_order" if j == len(aux) - 1 else "inv_between_primaries"] += 1
     for j in range(1, len(aux) - 1):
         v = r[aux[j] & 0xffffffff]
@@ -236,6 +288,14 @@ def post_read(opt, rep_len, regs, extra, cigars):
     out = np.zeros(len(r), REG_DTYPE)
     for k in REG_DTYPE.names:
         out[k] = r[k]
+    lens = [len(cigars[i]) for i in src]
+    for m in (64, 65):
+        if m in lens:
+            cover["cigar_%d_words" % m] += 1
+    if lens and min(lens) == 0 < max(lens):
+        cover["cigar_none_beside_some"] += 1
+    if len(r) > 64:
+        cover["final_over_64"] += 1
     return out, extra[src].copy(), dp2[src].astype(np.int32), [np.asarray(cigars[i], np.uint32) for i in src]
 
 

@@ -29,9 +29,9 @@ def same(u, v):
 
 
 def inputs(name):
-    """(golden, opt dict, rep_len, regs_off, regs, extra, cigar_off, cigar) of a scene, synthetic or real."""
+    """(golden, opt dict, rep_len, regs_off, regs, extra, cigar_off, cigar) of a scene, synthetic (the edge tier's too) or real."""
     g = PS.load(name)
-    if name in PS.SYNTHETIC:
+    if name not in PS.REAL:
         src = g
         arrs = [g[k] for k in ("regs_off", "regs", "extra", "cigar_off", "cigar")]
     else:
@@ -157,7 +157,7 @@ def test_debug_check_refusals():
     assert _check(extra=ex)[0] == -1                                             # has_extra outside 0 / 1
 
 
-@pytest.mark.parametrize("match_sc,kmax", [(1, 1 << 20), (4, 1 << 20), (2, 1 << 24)])
+@pytest.mark.parametrize("match_sc,kmax", [(1, 1 << 20), (4, 1 << 20), (2, 1 << 24), (3, 1 << 20), (5, 1 << 20)])
 def test_logf_patch_list_reproduces_host_logf(match_sc, kmax):
     """(float)log((double)x) for x = (float)k / (float)match_sc, patched at the listed k, is the host's logf(x) for every k in [1, kmax];
     the list is built over [1, 2^24] whatever kmax is."""
