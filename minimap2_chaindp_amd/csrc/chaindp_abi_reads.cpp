@@ -245,7 +245,8 @@ int chaindp::align_reads_compute(chaindp_ctx *ctx, const chaindp_align_opt_t *op
 	const size_t L = ctx->rd_item.size(), R = (size_t)n_reads;
 	Carve ls;
 	const size_t o_loff = ls.take((R + 1) * 8), o_item = ls.take(L * 4), o_key = ls.take(L * 8), o_cat = ls.take(L * 8), o_placed = ls.take(L * 4), o_final = ls.take(L * 4),
-	             o_skey = ls.take(L * 8), o_mark = ls.take(L * 4), o_cnt = ls.take(R * 4), o_words = ls.take(R * 8), o_woff = ls.take((R + 1) * 8), o_src = ls.take(L * 4);
+	             o_skey = ls.take(L * 8), o_mark = ls.take(L * 4), o_cnt = ls.take(R * 4), o_words = ls.take(R * 8), o_woff = ls.take((R + 1) * 8), o_src = ls.take(L * 4),
+	             o_tied = ls.take(R * 4), o_pairs = ls.take(L * 16), o_stack = ls.take((size_t)reads_tied_stack((int64_t)L, n_reads) * 12);
 	if ((rc = ksw_grow(ctx, ctx->rd_list, ls.at + 16, "the lists", WHO))) return rc;
 	Carve ot;
 	const size_t o_ooff = ot.take((R + 1) * 8), o_need = ot.take(16), o_oregs = ot.take(L * 80), o_oextra = ot.take(L * 20), o_coff = ot.take((L + 1) * 8);
@@ -262,7 +263,7 @@ int chaindp::align_reads_compute(chaindp_ctx *ctx, const chaindp_align_opt_t *op
 	d.rec = (const int32_t*)ctx->rd_rec[ctx->rd_rec_cur].p; d.cig = (const uint32_t*)ctx->rd_cig[ctx->rd_cig_cur].p;
 	d.placed = (int32_t*)(d_ls + o_placed); d.final_order = (int32_t*)(d_ls + o_final); d.sort_key = (unsigned long long*)(d_ls + o_skey);
 	d.mark = (uint32_t*)(d_ls + o_mark); d.cnt = (int32_t*)(d_ls + o_cnt); d.words = (int64_t*)(d_ls + o_words); d.word_off = (int64_t*)(d_ls + o_woff);
-	d.src = (int32_t*)(d_ls + o_src);
+	d.src = (int32_t*)(d_ls + o_src); d.tied = (int32_t*)(d_ls + o_tied); d.pairs = d_ls + o_pairs; d.stack = d_ls + o_stack;
 	d.out_off = (int64_t*)(d_ot + o_ooff); d.need = (int64_t*)(d_ot + o_need); d.out_regs = (int32_t*)(d_ot + o_oregs); d.out_extra = (int32_t*)(d_ot + o_oextra);
 	d.cigar_off = (int64_t*)(d_ot + o_coff); d.out_cig = (uint32_t*)ctx->rd_out_cig.p;
 	HIP_TRY(ctx, host_copy(d_ls + o_loff, ctx->rd_list_off.data(), (R + 1) * 8, hipMemcpyHostToDevice, st));

@@ -408,11 +408,15 @@ struct ReadsDev {
 	const int32_t *rec; const uint32_t *cig;
 	// work: the placed order and the final order as list indices, the global route's sort keys and marks, per read the final regions and words
 	int32_t *placed, *final_order; unsigned long long *sort_key; uint32_t *mark; int32_t *cnt; int64_t *words, *word_off; int32_t *src;
+	// ... and for the reads whose final order rests on how radix_sort_128x leaves equal keys (tied[n_reads]): their (sort key, place)
+	// pairs, n_listed of them, and the sort's pending ranges, reads_tied_stack(n_listed, n_reads) of 12 bytes each
+	int32_t *tied; void *pairs, *stack;
 	// the resident result: out_off[n_reads + 1], need[2], regs, extra, cigar_off[n_listed + 1], the CIGAR words
 	int64_t *out_off, *need; int32_t *out_regs, *out_extra; int64_t *cigar_off; uint32_t *out_cig;
 };
 hipError_t launch_reads_keep(hipStream_t st, int64_t n, const int32_t *d_regs, const int32_t *d_extra, int32_t *d_rec);
 // lds_cap: lists of up to so many records are ranked in LDS (at most RD_LDS_CAP), longer ones through sort_key and mark
+// (k_reads_finish, then k_reads_tied for the reads it flagged, k_reads_scan, k_reads_order)
 hipError_t launch_reads_finish(hipStream_t st, const AlignOpt &o, const ReadsDev &d, int lds_cap);
 hipError_t launch_reads_gather(hipStream_t st, const ReadsDev &d);
 

@@ -28,6 +28,10 @@ RD_HD inline uint64_t reads_place_key(uint32_t origin, uint32_t born, uint32_t i
 	return (uint64_t)origin << 32 | (uint64_t)born << 1 | (uint64_t)(is_inv & 1u);
 }
 
+// Pending ranges of radix_sort_128x (chaindp_rsort.h: n / 65 + 2 for a list of n) for every read of a batch at once: read r's lie at
+// list_off[r] / 65 + 2 r.
+RD_HD inline int64_t reads_tied_stack(int64_t n_listed, int64_t n_reads) { return n_listed / 65 + 2 * n_reads + 2; }
+
 // a record of the pool, in pool order: round 0's regions, round 1's, ..., then one per slot of the inversion call
 struct ReadsRec { int32_t read, origin, born, is_inv; };
 

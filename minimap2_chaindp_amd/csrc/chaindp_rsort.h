@@ -23,11 +23,10 @@ __device__ inline void bt_insertion(ulonglong2 *beg, ulonglong2 *end)
 
 struct BtRange { int32_t beg, end, shift; };
 
-// stack: room for n / 65 + 2 pending ranges
-__device__ inline void bt_radix_128x(ulonglong2 *a, int32_t n, BtRange *stack)
+// stack: room for n / 65 + 2 pending ranges; head, tail: the digit tables, 256 entries each, where the caller keeps them
+__device__ inline void bt_radix_128x(ulonglong2 *a, int32_t n, BtRange *stack, int32_t *head, int32_t *tail)
 {
 	if (n <= 64) { bt_insertion(a, a + n); return; }
-	int32_t head[256], tail[256];
 	int sp = 0;
 	stack[sp++] = BtRange{0, n, 56};
 	while (sp > 0) {
@@ -60,6 +59,13 @@ __device__ inline void bt_radix_128x(ulonglong2 *a, int32_t n, BtRange *stack)
 			}
 		}
 	}
+}
+
+// ... with the digit tables the thread's own
+__device__ inline void bt_radix_128x(ulonglong2 *a, int32_t n, BtRange *stack)
+{
+	int32_t head[256], tail[256];
+	bt_radix_128x(a, n, stack, head, tail);
 }
 
 } // namespace chaindp

@@ -6,7 +6,11 @@
 //   k_reads_keep     a round's regions and extras into pool records
 //   k_reads_finish   a wave per read: the placed order by rank of the place key; mm_filter_regs (hit.c:249-268, max_clip_ratio 1.0);
 //                    mm_hit_sort_by_dp (hit.c:167-193): nothing for a list of one, else cnt == 0 && !inv dropped and the rest ranked by
-//                    dp_max << 32 | hash falling, equal keys in placed order; the read's final regions and CIGAR words counted
+//                    dp_max << 32 | hash falling, of equal keys the later placed one first: radix_sort_128x's insertion sort for up to
+//                    64 live records is stable, and the list is reversed behind it.  More than 64 live records with equal keys among
+//                    them are flagged and their (key, place) pairs written out; the read's final regions and CIGAR words counted
+//   k_reads_tied     a wave per flagged read: one lane takes the pairs through bt_radix_128x (chaindp_rsort.h, the digit tables in
+//                    LDS), which leaves equal keys where the reference's in-place procedure does; the final order is that, reversed
 //   k_reads_scan     the reads' counts to out_off and to the reads' first CIGAR word, one workgroup
 //   k_reads_order    a wave per read: every final region's list index and its CIGAR offset
 //   k_reads_gather   records and extras word by word, k_reads_gather_cig a wave per region: coalesced, grid-strided stores
@@ -17,6 +21,7 @@
 #include "../chaindp_wave.h"
 #include "../chaindp_post_dev.h"
 #include "../chaindp_reads_plan.h"
+#include "../chaindp_rsort.h"
 
 namespace chaindp {
 
@@ -50,7 +55,7 @@ __device__ __forceinline__ uint32_t reads_mark(const AlignOpt &o, int qlen, cons
 template <typename KI, typename KO, typename I, typename M>
 __device__ __forceinline__ void reads_finish_one(const AlignOpt &o, int lane, int n, int qlen, int64_t base, KI key, const int32_t *__restrict__ item,
                                                  const int32_t *__restrict__ rec, I it, KO k2, M mk, int32_t *__restrict__ placed, int32_t *__restrict__ final_order,
-                                                 int32_t *cnt_out, int64_t *words_out)
+                                                 int32_t *cnt_out, int64_t *words_out, int32_t *tied_out, ulonglong2 *__restrict__ pairs)
 {
 	// the placed order, and at each place the record's verdict and sort key
 	for (int i = lane; i < n; i += 64) {
@@ -68,13 +73,17 @@ __device__ __forceinline__ void reads_finish_one(const AlignOpt &o, int lane, in
 	for (int p = lane; p < n; p += 64) kept += mk[p] != RD_FILTERED;
 	kept = wave_sum_i(kept);
 	const uint32_t live_from = kept <= 1 ? RD_SOFT_DELETED : RD_LIVE;        // mm_hit_sort_by_dp returns at once when n <= 1
-	int n_final = 0;
+	int n_final = 0, tie = 0;
 	long long words = 0;
 	for (int p = lane; p < n; p += 64) {
 		if (mk[p] < live_from) continue;
 		const unsigned long long kp = k2[p];
 		int rank = 0;
-		for (int q = 0; q < n; ++q) rank += mk[q] >= live_from && (k2[q] > kp || (k2[q] == kp && q < p));
+		for (int q = 0; q < n; ++q) {
+			const bool live = mk[q] >= live_from, same = k2[q] == kp;
+			rank += live && (k2[q] > kp || (same && q > p));
+			tie |= live && same && q != p;
+		}
 		final_order[base + rank] = it[p];
 		++n_final;
 		words += max(rec[(int64_t)item[it[p]] * RD_REC_WORDS + AL_REG_WORDS + 4], 0);
@@ -82,7 +91,16 @@ __device__ __forceinline__ void reads_finish_one(const AlignOpt &o, int lane, in
 	n_final = wave_sum_i(n_final);
 	long long w64 = words;
 	for (int d = 32; d; d >>= 1) w64 += __shfl_xor(w64, d);
-	if (lane == 0) { *cnt_out = n_final; *words_out = w64; }
+	// the threshold is radix_sort_128x's, on the live records (n_aux): past it equal keys end where its in-place procedure leaves them
+	const int tied = n_final > 64 && wave_sum_i(tie) != 0;
+	if (tied)
+		for (int p = lane; p < n; p += 64) {
+			if (mk[p] < RD_LIVE) continue;
+			int at = 0;
+			for (int q = 0; q < p; ++q) at += mk[q] >= RD_LIVE;
+			pairs[base + at] = make_ulonglong2(k2[p], (unsigned long long)p);     // the live records in placed order, as aux[] holds them
+		}
+	if (lane == 0) { *cnt_out = n_final; *words_out = w64; *tied_out = tied; }
 }
 
 __global__ __launch_bounds__(64) void k_reads_finish(AlignOpt o, ReadsDev d, int lds_cap)
@@ -100,11 +118,29 @@ __global__ __launch_bounds__(64) void k_reads_finish(AlignOpt o, ReadsDev d, int
 			for (int i = lane; i < n; i += 64) s_key[i] = d.key[base + i];
 			__syncthreads();
 			reads_finish_one(o, lane, n, qlen, base, (unsigned long long*)s_key, d.item, d.rec, (int32_t*)s_it, (unsigned long long*)s_k2, (uint32_t*)s_mk,
-			                 d.placed, d.final_order, d.cnt + r, d.words + r);
+			                 d.placed, d.final_order, d.cnt + r, d.words + r, d.tied + r, (ulonglong2*)d.pairs);
 		} else {
 			reads_finish_one(o, lane, n, qlen, base, (const unsigned long long*)(d.key + base), d.item, d.rec, d.src + base, d.sort_key + base,      // src: free until k_reads_order
-			                 d.mark + base, d.placed, d.final_order, d.cnt + r, d.words + r);
+			                 d.mark + base, d.placed, d.final_order, d.cnt + r, d.words + r, d.tied + r, (ulonglong2*)d.pairs);
 		}
+	}
+}
+
+// The reads k_reads_finish flagged: pairs[base .. base + cnt) are the live records' (key, place) in placed order and placed[] names the
+// record at every place.  radix_sort_128x is sequential; the other lanes wait and then write the order out, last first.
+__global__ __launch_bounds__(64) void k_reads_tied(ReadsDev d)
+{
+	__shared__ int32_t s_head[256], s_tail[256];
+	const int lane = threadIdx.x;
+	for (int64_t r = blockIdx.x; r < d.n_reads; r += gridDim.x) {
+		if (!d.tied[r]) continue;
+		const int64_t base = d.list_off[r];
+		const int m = d.cnt[r];
+		ulonglong2 *a = (ulonglong2*)d.pairs + base;
+		if (lane == 0) bt_radix_128x(a, m, (BtRange*)d.stack + base / 65 + 2 * r, s_head, s_tail);
+		__syncthreads();
+		for (int i = lane; i < m; i += 64) d.final_order[base + m - 1 - i] = d.placed[base + (int64_t)a[i].y];
+		__syncthreads();
 	}
 }
 
@@ -198,6 +234,8 @@ hipError_t launch_reads_finish(hipStream_t st, const AlignOpt &o, const ReadsDev
 	hipLaunchKernelGGL(k_reads_finish, dim3(reads_grid(d.n_reads)), dim3(64), 0, st, o, d, lds_cap < RD_LDS_CAP ? lds_cap : RD_LDS_CAP);
 	hipError_t e = hipGetLastError();
 	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(k_reads_tied, dim3(reads_grid(d.n_reads)), dim3(64), 0, st, d);
+	if ((e = hipGetLastError()) != hipSuccess) return e;
 	hipLaunchKernelGGL(k_reads_scan, dim3(1), dim3(256), 0, st, d);
 	if ((e = hipGetLastError()) != hipSuccess) return e;
 	hipLaunchKernelGGL(k_reads_order, dim3(reads_grid(d.n_reads)), dim3(64), 0, st, d);

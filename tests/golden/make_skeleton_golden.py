@@ -12,7 +12,7 @@ align1 rounds and the inversion call), for the GPU tier to hold the device's int
 
 Asserts on the way: mm_squeeze_a leaves every scene's anchors where they are (in the driver, on a copy); the batched composition
 (tests/skeleton_model.py over align_model and inv_model) equals the reference in every word on every read; no scene is refused
-(unspecified behaviour, a region sorted without an alignment, equal sort keys); every class of skeleton_model.COVER occurred."""
+(unspecified behaviour, a region sorted without an alignment); every class of skeleton_model.COVER occurred."""
 import ctypes as C
 import os
 import shutil
@@ -36,7 +36,7 @@ TRACED = dict(align1=("regs_off", "regs_in", "a", "regs", "regs2", "extra", "cig
 
 DRIVER = r"""
 /* mm_align_skeleton's call of mm_filter_regs goes through a tap of the driver's, which copies the list as the loop left it (the sort
- * orders by distinct keys and hides where a record stood) and then calls the reference's mm_filter_regs */
+ * hides where a record stood) and then calls the reference's mm_filter_regs */
 #define mm_filter_regs drv_tap_filter_regs
 #include "%(ref)s/align.c"
 #undef mm_filter_regs

@@ -7,9 +7,9 @@ the CPU tier and the GPU tier run the same loop code and differ only in the stag
 run() composes them the way a batched host must: round 0 aligns every region of every read, round k exactly the regions round k - 1
 split off (regs2.cnt > 0) with the anchors as round k - 1 returned them, until nothing is split off; each split-off region stands
 behind its parent (mm_insert_reg); one inv_batch call over the final lists; every made == 1 record behind its right region; then
-mm_filter_regs (hit.c:249-268, max_clip_ratio at mm_mapopt_init's 1.0) and mm_hit_sort_by_dp (hit.c:167-193) as restatements.  The sort
-orders by distinct keys, so where a record stood in the list cannot be read off the final regions: run() also returns the list as it
-stands before the filter, which the golden generator records from the reference's own loop.
+mm_filter_regs (hit.c:249-268, max_clip_ratio at mm_mapopt_init's 1.0) and mm_hit_sort_by_dp (hit.c:167-193) as restatements, the sort
+with the order radix_sort_128x gives equal keys (sort_pairs).  Where a record stood in the list cannot be read off the final regions:
+run() also returns the list as it stands before the filter, which the golden generator records from the reference's own loop.
 tests/golden/make_skeleton_golden.py proves run() over the CPU models equal to the compiled mm_align_skeleton before the goldens are
 trusted.  Every loop case the tests name is counted in `cover`; the counters change no result."""
 import collections
@@ -30,10 +30,6 @@ COVER = ("rounds_1", "rounds_2", "rounds_3plus", "r2_range_has_ignored_seed", "r
 OUTPUTS = ("placed_off", "placed", "regs_off", "regs", "extra", "cigar_off", "cigar", "a")
 
 cover = collections.Counter()
-
-
-class SortTie(Exception):
-    """Two regions of a read share dp_max << 32 | hash: the expected order would rest on how the sort treats equal keys."""
 
 
 def offsets(lens):
@@ -80,19 +76,79 @@ def filter_regs(opt, qlen, slots):
     return kept
 
 
+def _insertion(a, beg, end):
+    """Rising by key, an element moved only past strictly larger ones: equal keys keep their order."""
+    for i in range(beg + 1, end):
+        if a[i][0] < a[i - 1][0]:
+            t, j = a[i], i
+            while j > beg and t[0] < a[j - 1][0]:
+                a[j] = a[j - 1]
+                j -= 1
+            a[j] = t
+
+
+def sort_pairs(pairs, top=64):
+    """The order the reference's radix_sort_128x (ksort.h:101-151) leaves (key, y) pairs in, rising by key, as csrc/chaindp_rsort.h follows
+    it: up to 64 pairs by insertion, stable; more in place, byte by byte from the top one -- count the range's digits, walk the buckets
+    upwards and carry each element that lies in a wrong bucket to the next free place of its own, taking up what lies there, until one
+    comes back for the place the walk left; then every bucket of more than 64 is a range of the next byte and every one of 2 to 64 is
+    sorted by insertion.  Equal keys end where the carrying left them.  top: the first threshold, for a test to move."""
+    a = list(pairs)
+    if len(a) <= top:
+        _insertion(a, 0, len(a))
+        return a
+    stack = [(0, len(a), 56)]
+    while stack:
+        beg, end, shift = stack.pop()
+        digit = lambda q: a[q][0] >> shift & 0xff
+        tail = [0] * 256
+        for q in range(beg, end):
+            tail[digit(q)] += 1
+        head, acc = [0] * 256, beg
+        for d in range(256):
+            head[d] = acc
+            acc += tail[d]
+            tail[d] = acc
+        d = 0
+        while d < 256:
+            if head[d] == tail[d]:
+                d += 1
+                continue
+            to = digit(head[d])
+            if to != d:
+                carry = a[head[d]]
+                while to != d:
+                    carry, a[head[to]] = a[head[to]], carry
+                    head[to] += 1
+                    to = carry[0] >> shift & 0xff
+                a[head[d]] = carry
+            head[d] += 1
+        if shift:
+            b = beg
+            for d in range(256):
+                e = tail[d]
+                if e - b > 64:
+                    stack.append((b, e, max(shift - 8, 0)))
+                elif e - b > 1:
+                    _insertion(a, b, e)
+                b = e
+    return a
+
+
 def hit_sort_by_dp(slots):
-    """mm_hit_sort_by_dp over one read's slots: by dp_max << 32 | hash, falling."""
+    """mm_hit_sort_by_dp over one read's slots: by dp_max << 32 | hash, falling; equal keys as radix_sort_128x over the live regions and
+    the reversal behind it leave them (up to 64 live regions: the later one first)."""
     if len(slots) <= 1:
         return slots
     live = [s for s in slots if int(s["reg"]["bits"][0]) & BIT_INV or int(s["reg"]["cnt"][0]) > 0]
     if not all(s["extra"]["has_extra"][0] for s in live):
         raise A.Undefined("a region reaches the sort with p == NULL")
     keys = [int(s["extra"]["dp_max"][0]) << 32 | int(s["reg"]["hash"][0]) for s in live]
-    if len(set(keys)) != len(keys):
-        raise SortTie(keys)
-    order = sorted(range(len(live)), key=lambda i: -keys[i])
+    order = [i for _, i in sort_pairs(list(zip(keys, range(len(live)))))][::-1]
     if order != list(range(len(live))):
         cover["sort_changes_order"] += 1
+    if len(set(keys)) != len(keys):
+        cover["sort_key_tie"] += 1
     return [live[i] for i in order]
 
 
@@ -101,7 +157,7 @@ def run(opt, reads, align1_batch, inv_batch, trace=None):
     Returns dict(placed_off, placed, regs_off, regs, extra, cigar_off, cigar, a): each read's list as the loop leaves it for
     mm_filter_regs (split-off regions and inversions in their places; the sort hides the places afterwards), its final regions (every
     word of REG_DTYPE), what r->p holds beside the CIGAR, the CIGARs as CSR over the regions, and the anchors with their marks (a_off
-    is the input's).  trace, a list, gets one dict per stage call with its inputs and outputs."""
+    is the input's); beside these OUTPUTS placed_extra, what r->p holds for every record of placed.  trace, a list, gets one dict per stage call with its inputs and outputs."""
     seq_off, seq = offsets([len(rd["seq"]) for rd in reads]), _cat([np.asarray(rd["seq"], np.uint8) for rd in reads], np.uint8)
     a_off = offsets([len(rd["a"]) for rd in reads])
     a = _cat([np.asarray(rd["a"], np.uint64).reshape(-1, 2) for rd in reads], np.uint64).reshape(-1, 2)
@@ -170,6 +226,7 @@ def run(opt, reads, align1_batch, inv_batch, trace=None):
             g += 1
         final.append(out)
     placed_off, placed = offsets([len(l) for l in final]), _cat([s["reg"] for l in final for s in l], REG_DTYPE)
+    placed_extra = _cat([s["extra"] for l in final for s in l], EXTRA_DTYPE)
     for rd, l in enumerate(final):
         final[rd] = l = hit_sort_by_dp(filter_regs(opt, int(seq_off[rd + 1] - seq_off[rd]), l))
         for s in l:
@@ -177,7 +234,7 @@ def run(opt, reads, align1_batch, inv_batch, trace=None):
         if len({int(s["reg"]["rid"][0]) for s in l}) > 1:
             cover["read_on_two_targets"] += 1
     flat = [s for l in final for s in l]
-    return dict(placed_off=placed_off, placed=placed, regs_off=offsets([len(l) for l in final]), regs=_cat([s["reg"] for s in flat], REG_DTYPE), extra=_cat([s["extra"] for s in flat], EXTRA_DTYPE),
+    return dict(placed_off=placed_off, placed=placed, placed_extra=placed_extra, regs_off=offsets([len(l) for l in final]), regs=_cat([s["reg"] for s in flat], REG_DTYPE), extra=_cat([s["extra"] for s in flat], EXTRA_DTYPE),
                 cigar_off=offsets([len(s["cigar"]) for s in flat]), cigar=_cat([s["cigar"] for s in flat], np.uint32), a=a)
 
 

@@ -2,8 +2,9 @@
 about 1500 bases, anchors on the true path, regions over them), each at the smallest size that reaches its loop case, and a seeded
 fuzz.  Every read's anchors are as mm_squeeze_a leaves them: the regions' anchor ranges follow each other from 0 without a hole.
 
-check() refuses a scene that falls into unspecified behaviour of align1 or align1_inv (align_model.Undefined), in which a surviving
-region would reach the sort without an alignment, or in which two regions of a read share the sort key (skeleton_model.SortTie)."""
+check() refuses a scene that falls into unspecified behaviour of align1 or align1_inv (align_model.Undefined) or in which a surviving
+region would reach the sort without an alignment.  Regions of a read that share the sort key are ordered as the reference's sort
+leaves them (skeleton_model.sort_pairs); the scenes here have none, the tie scenes of align_reads_shapes.py do."""
 import zlib
 
 import numpy as np
@@ -163,4 +164,4 @@ def squeezed(p):
 def check(p, trace=None):
     """The scene through the loop over the CPU models: raises where the scene is refused, returns run()'s outputs otherwise."""
     assert squeezed(p), "the anchors are not as mm_squeeze_a leaves them"
-    return K.run_scene(p, trace=trace)           # align_model.Undefined and skeleton_model.SortTie pass through
+    return K.run_scene(p, trace=trace)           # align_model.Undefined passes through

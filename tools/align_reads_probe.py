@@ -30,14 +30,6 @@ import skeleton_shapes as SS  # noqa: E402
 from minimap2_chaindp_amd import chaindp, params  # noqa: E402
 
 
-def sort_keeping_ties(slots):
-    """skeleton_model.hit_sort_by_dp without its refusals: equal keys keep their placed order, as the call documents."""
-    if len(slots) <= 1:
-        return slots
-    live = [s for s in slots if int(s["reg"]["bits"][0]) & K.BIT_INV or int(s["reg"]["cnt"][0]) > 0]
-    return sorted(live, key=lambda s: -(int(s["extra"]["dp_max"][0]) << 32 | int(s["reg"]["hash"][0])))
-
-
 def nbytes(*arrays):
     return int(sum(np.asarray(x).nbytes for x in arrays))
 
@@ -47,7 +39,6 @@ def main():
     ap.add_argument("--reads", type=int, default=3000)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "align_reads_probe.json"))
     args = ap.parse_args()
-    K.hit_sort_by_dp = sort_keeping_ties
     g = SS.pack(SS.fuzz_scene(seed=11, n_reads=args.reads))
     opt = params.AlignOpt(*(int(v) for v in g["opt"]))
     import torch
