@@ -433,4 +433,5 @@ int chaindp_set_variant(chaindp_ctx_t *ctx, int force_general);
 #include "chaindp_align_inv.h"
 #include "chaindp_align_reads.h"
 #include "chaindp_align_post.h"
+#include "chaindp_map_align.h"
 #endif

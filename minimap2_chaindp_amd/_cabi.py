@@ -1,4 +1,4 @@
-"""ctypes prototypes of the C ABI, read from the headers under include/ (chaindp.h, chaindp_gaps.h, chaindp_debug.h, chaindp_fpga.h).
+"""ctypes prototypes of the C ABI, read from the headers under include/ (chaindp.h, chaindp_gaps.h, chaindp_debug.h, chaindp_fpga.h, and the stage headers chaindp.h includes).
 
 The headers are the one place a prototype is written down: parse() turns a header's text into {name: (restype, [argtypes])} and
 bind() sets them on the loaded library.  It reads these headers, it is not a C parser: a declaration or a type it does not

@@ -53,7 +53,7 @@ _lib = None
 
 
 def lib():
-    """The library, every function of include/chaindp.h, chaindp_gaps.h, chaindp_ksw.h, chaindp_align.h, chaindp_align_inv.h, chaindp_align_reads.h, chaindp_align_post.h and chaindp_debug.h bound with the
+    """The library, every function of include/chaindp.h, chaindp_gaps.h, chaindp_ksw.h, chaindp_align.h, chaindp_align_inv.h, chaindp_align_reads.h, chaindp_align_post.h, chaindp_map_align.h and chaindp_debug.h bound with the
     header's prototype."""
     global _lib
     if _lib is None:
@@ -61,7 +61,7 @@ def lib():
             raise ChainDPError(f"{LIB_PATH} is missing: build it with __graft_entry__.build() "
                                "(make -C minimap2_chaindp_amd/csrc); there is no fallback path")
         _lib = _cabi.bind(C.CDLL(LIB_PATH), "chaindp.h", "chaindp_gaps.h", "chaindp_ksw.h", "chaindp_align.h", "chaindp_align_inv.h", "chaindp_align_reads.h",
-                          "chaindp_align_post.h", "chaindp_debug.h")
+                          "chaindp_align_post.h", "chaindp_map_align.h", "chaindp_debug.h")
     return _lib
 
 
@@ -155,6 +155,12 @@ _CAPS = {
     "align_post_cigar":  _Cap("n_words", 1, True, "raise", "align_post_fetch", None),
     "align_reads_post":       _Cap("n_regs2", 1, True, "raise", "align_post_fetch", None),
     "align_reads_post_cigar": _Cap("n_bases", 4, True, "raise", "align_post_fetch", None),
+    # align_resident works on what chain_post left on the device: the host knows the reads and the batch's anchors, guesses two regions a
+    # read and a CIGAR word per anchor; map_align_seqs knows the bases alone.  Both results stay resident: the fetch makes a guess good
+    "align_resident":        _Cap("n_reads2", 1,  True, "raise", "align_post_fetch", None),
+    "align_resident_cigar":  _Cap("total",    1,  True, "raise", "align_post_fetch", None),
+    "map_align_seqs":        _Cap("n_bases",  32, True, "raise", "align_post_fetch", None),
+    "map_align_seqs_cigar":  _Cap("n_bases",  4,  True, "raise", "align_post_fetch", None),
     "ksw_extd":      _Cap("n_span",  1,  False, "raise", None,         None),      # room for q_len + t_len words a problem: never short
 }
 
@@ -793,6 +799,97 @@ class Device:
             return rc
         return (a_out, *self._finished(("align_reads_post", "align_reads_post_cigar"), (regs_cap, cigar_cap), dict(n_regs2=2 * n_regs, n_bases=len(seq)), n_reads,
                                        call, dict(a=a_out)))
+
+    # -- mapping with base alignment: chain_post's result handed to the alignment stages on the device (chaindp_map_align.h)
+    def _resident_anchors(self, n_reads):
+        """(a_off int64[n_reads + 1], a uint64[..., 2]): the squeezed anchors of the last align_resident / map_align_seqs with their marks."""
+        a_off = np.zeros(n_reads + 1, np.int64)
+        rc = self._lib.chaindp_align_resident_anchors(self._ctx, n_reads, _ptr(a_off), None, 0)
+        if rc != ERR_CAPACITY:
+            self._check(rc)
+        a = np.zeros((max(int(a_off[-1]), 1), 2), np.uint64)
+        self._check(self._lib.chaindp_align_resident_anchors(self._ctx, n_reads, _ptr(a_off), _ptr(a), len(a)))
+        return a_off, a[:int(a_off[-1])]
+
+    def align_resident(self, aopt, opt, regs_cap=None, cigar_cap=None, want_anchors=False):
+        """The rest of a read's path after chain_post(opt with MM_F_CIGAR) / map_reads / map_seqs on this batch, on the device
+        (chaindp_align_resident): the hand-off (mm_squeeze_a), align_reads and align_post on the resident bases of the batch's sketch(),
+        its resident rep_len and the targets of align_set_targets().  Returns (regs_off, regs, extra, dp_max2, cigar_off, cigar) as
+        align_post does and, with want_anchors, (a_off int64[n_reads + 1], a uint64[..., 2]) behind them: the squeezed anchors with the
+        marks of the alignment.  regs_cap / cigar_cap as in align_reads; a short cap of the caller's raises with err.regs_off / .need."""
+        n_reads = self._n_reads
+        # the anchors come with the call itself: the chain anchors are some of the batch's, whose number the host knows
+        a_off = np.zeros(n_reads + 1, np.int64) if want_anchors else None
+        a = np.zeros((max(self._total, 1), 2), np.uint64) if want_anchors else None
+
+        def call(*room):
+            rc = self._lib.chaindp_align_resident(self._ctx, C.byref(aopt), C.byref(opt), n_reads, *room, _ptr(a_off), _ptr(a))
+            if rc in (0, ERR_CAPACITY):
+                self._align_reads_n = n_reads
+            return rc
+        out = self._finished(("align_resident", "align_resident_cigar"), (regs_cap, cigar_cap), dict(n_reads2=2 * n_reads, total=self._total), n_reads, call, {})
+        return (*out, a_off, a[:int(a_off[-1])]) if want_anchors else out
+
+    def map_align_seqs(self, index, w, k, is_hpc, flag, max_occ, par, min_cnt, opt, aopt, seq, seq_off, bid, hash_, ref_len, regs_cap=None, cigar_cap=None,
+                       want_anchors=False, gaps=None):
+        """Bases in, the final hits of a run with MM_F_CIGAR and their CIGARs out (chaindp_map_align_seqs = map_seqs() with opt.flag |
+        MM_F_CIGAR + align_resident()): (regs_off, regs, extra, dp_max2, cigar_off, cigar, rep_len int32[n_reads], n_anchors) and, with
+        want_anchors, (a_off, a) behind them.  The targets must have been set with align_set_targets()."""
+        seq, seq_off = self._seqs(seq, seq_off)
+        n_reads = len(seq_off) - 1
+        bid, hash_, ref_len = _arr(bid, np.uint32), _arr(hash_, np.uint32), _arr(ref_len, np.int32)
+        rep, na = np.zeros(max(n_reads, 1), np.int32), C.c_int64(0)
+
+        def call(*room):
+            rc = self._lib.chaindp_map_align_seqs(self._ctx, index, int(w), int(k), int(bool(is_hpc)), int(flag), int(max_occ), C.byref(par), int(min_cnt),
+                                                  C.byref(opt), C.byref(aopt), n_reads, _ptr(seq_off), _ptr0(seq), _ptr(bid), _ptr(hash_), _ptr0(ref_len),
+                                                  len(ref_len), *room, None, None, _ptr(rep), C.byref(na))
+            if rc in (0, ERR_CAPACITY) or na.value:                           # a call refused at its entry left the resident batch as it was
+                self._n_reads, self._total = n_reads, int(na.value)
+            if rc in (0, ERR_CAPACITY):
+                self._align_reads_n = n_reads
+            return rc
+        with self._gaps(gaps):
+            out = self._finished(("map_align_seqs", "map_align_seqs_cigar"), (regs_cap, cigar_cap), dict(n_bases=len(seq)), n_reads, call, {})
+        out = (*out, rep[:n_reads], int(na.value))
+        return (*out, *self._resident_anchors(n_reads)) if want_anchors else out
+
+    def map_align_handoff(self):
+        """The regions as the hand-off of the last align_resident / map_align_seqs left them, before any alignment (test hook): (regs_off
+        int64[n_reads + 1], regs REG_DTYPE[...] with `as` into the squeezed anchors, a_off int64[n_reads + 1])."""
+        n_reads = self._n_reads
+        roff, aoff = np.zeros(n_reads + 1, np.int64), np.zeros(n_reads + 1, np.int64)
+        rc = self._lib.chaindp_map_align_debug_handoff(self._ctx, n_reads, _ptr(roff), None, 0, _ptr(aoff))
+        if rc != ERR_CAPACITY:
+            self._check(rc)
+        regs = np.zeros(max(int(roff[-1]), 1), REG_DTYPE)
+        self._check(self._lib.chaindp_map_align_debug_handoff(self._ctx, n_reads, _ptr(roff), _ptr(regs), len(regs), _ptr(aoff)))
+        return roff, regs[:int(roff[-1])], aoff
+
+    def map_align_run_handoff(self, regs_off, regs, b_off, b):
+        """The hand-off alone on regions and anchors from the host, in the form chain_post(want_anchors=True) returns them (test hook):
+        (regs REG_DTYPE[...] with their new `as`, a_off int64[n_reads + 1], a uint64[..., 2])."""
+        regs_off, regs, b_off, b = _arr(regs_off, np.int64), _arr(regs, REG_DTYPE), _arr(b_off, np.int64), _arr(b, np.uint64).reshape(-1, 2)
+        if len(regs_off) != len(b_off) or int(regs_off[-1]) != len(regs) or int(b_off[-1]) != len(b):
+            raise ValueError("regs_off and b_off need one entry per read and one more and must end at the sizes of regs and b")
+        out, a_off, a = np.zeros(max(len(regs), 1), REG_DTYPE), np.zeros(len(regs_off), np.int64), np.zeros((max(len(b), 1), 2), np.uint64)
+        self._check(self._lib.chaindp_map_align_debug_run_handoff(self._ctx, len(regs_off) - 1, _ptr(regs_off), _ptr0(regs), _ptr(b_off), _ptr0(b), _ptr(out),
+                                                                 _ptr(a_off), _ptr(a)))
+        return out[:len(regs)], a_off, a[:int(a_off[-1])]
+
+    def map_align_ms(self):
+        """Device milliseconds of the last align_resident / map_align_seqs made while profiling was on (tuning hook): dict of handoff,
+        then align_reads_ms()'s rounds, inv, finish, gather and align_post_ms()'s read, post_gather."""
+        ms = (C.c_double * 7)()
+        self._check(self._lib.chaindp_map_align_debug_ms(self._ctx, ms))
+        return dict(zip(("handoff", "rounds", "inv", "finish", "gather", "read", "post_gather"), (float(x) for x in ms)))
+
+    def map_align_set_lds_cap(self, cap=0):
+        """Test hook: later hand-offs rank lists of up to `cap` regions in LDS and longer ones in global memory; 0: the built-in cap,
+        which is returned."""
+        out = np.zeros(1, np.int32)
+        self._check(self._lib.chaindp_map_align_debug_set_lds_cap(self._ctx, int(cap), _ptr(out)))
+        return int(out[0])
 
     def align_post_ms(self):
         """Device milliseconds of the last align_post / align_reads_post made while profiling was on (tuning hook): dict of read (the one

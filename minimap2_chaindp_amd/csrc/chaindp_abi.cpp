@@ -33,6 +33,7 @@ hipError_t chaindp::dev_grow(chaindp_ctx *ctx, DevGrow &g, size_t need)
 void chaindp::begin_batch(chaindp_ctx *ctx, int64_t n_reads, int64_t total, bool mp_resident)
 {
 	ctx->n_reads = n_reads; ctx->total = total; ctx->ran = false; ctx->ran_gaps = false; ctx->bot_n_reads = -1; ctx->mp_resident = mp_resident;
+	ctx->post_n_reads = -1; ctx->from_sketch = false;
 }
 
 // the batch's per-read segment counts, if it has any, on the stream that carries its upload

@@ -151,9 +151,11 @@ static int deliver(chaindp_ctx *ctx, const char *who, int64_t n_reads, int64_t *
 }
 
 // The stage over N regions with W CIGAR words of n_reads reads.  regs_off == nullptr: the regions are the resident result of
-// chaindp_align_reads; else they come up from the host arrays, which apost_check_regs has accepted.
+// chaindp_align_reads; else they come up from the host arrays, which apost_check_regs has accepted.  d_rep_len: rep_len is on the device
+// already (chaindp_align_resident) and the host's is not read.
 static int align_post_impl(chaindp_ctx *ctx, const char *who, const chaindp_post_opt_t *opt, int64_t n_reads, const int32_t *rep_len, int64_t N, int64_t W,
-                           const int64_t *regs_off, const chaindp_reg_t *regs, const chaindp_align_extra_t *extra, const int64_t *in_cigar_off, const uint32_t *in_cigar)
+                           const int64_t *regs_off, const chaindp_reg_t *regs, const chaindp_align_extra_t *extra, const int64_t *in_cigar_off, const uint32_t *in_cigar,
+                           const int32_t *d_rep_len = nullptr)
 {
 	ctx->ap_n_reads = -1;                                // whatever was resident is no longer
 	ctx->ap_need[0] = ctx->ap_need[1] = 0;
@@ -172,7 +174,7 @@ static int align_post_impl(chaindp_ctx *ctx, const char *who, const chaindp_post
 	if ((rc = ksw_grow(ctx, ctx->ap_out, L.out_bytes, "the result", who))) return rc;
 	if ((rc = ksw_grow(ctx, ctx->ap_out_cig, L.out_cig_bytes, "the result's CIGARs", who))) return rc;
 	char *d_in = (char*)ctx->ap_in.p, *d_w = (char*)ctx->ap_work.p, *d_o = (char*)ctx->ap_out.p;
-	HIP_TRY(ctx, host_copy(d_in + L.in_rep, rep_len, R * 4, hipMemcpyHostToDevice, st));
+	if (!d_rep_len) HIP_TRY(ctx, host_copy(d_in + L.in_rep, rep_len, R * 4, hipMemcpyHostToDevice, st));
 	ApostDev d = {};
 	d.n_reads = n_reads; d.n_regs = N;
 	if (from_host) {
@@ -190,7 +192,7 @@ static int align_post_impl(chaindp_ctx *ctx, const char *who, const chaindp_post
 		d.regs_off = (const int64_t*)(d_rd + ctx->rd_out_at[0]); d.regs = (const int32_t*)(d_rd + ctx->rd_out_at[1]); d.extra = (const int32_t*)(d_rd + ctx->rd_out_at[2]);
 		d.cigar_off = (const int64_t*)(d_rd + ctx->rd_out_at[3]); d.cig = (const uint32_t*)ctx->rd_out_cig.p;
 	}
-	d.rep_len = (const int32_t*)(d_in + L.in_rep);
+	d.rep_len = d_rep_len ? d_rep_len : (const int32_t*)(d_in + L.in_rep);
 	d.logf_k = ctx->d_logf_k; d.logf_v = ctx->d_logf_v; d.n_logf = ctx->n_logf;
 	d.dp_k = (const uint32_t*)ctx->ap_dp.p; d.dp_v = (const float*)((const char*)ctx->ap_dp.p + ((size_t)ctx->ap_n_dp * 4 + 15) / 16 * 16); d.n_dp = ctx->ap_n_dp;
 	d.cnt = (unsigned long long*)(d_w + L.w_cnt); d.words = (unsigned long long*)(d_w + L.w_words); d.tile = (unsigned long long*)(d_w + L.w_tile);
@@ -220,6 +222,17 @@ static int align_post_impl(chaindp_ctx *ctx, const char *who, const chaindp_post
 	ctx->ap_at[0] = L.w_cnt; ctx->ap_at[1] = L.o_regs; ctx->ap_at[2] = L.o_extra; ctx->ap_at[3] = L.o_dp2; ctx->ap_at[4] = L.o_cigar_off;
 	ctx->ap_n_reads = n_reads;
 	return CHAINDP_OK;
+}
+
+int chaindp::align_post_resident(chaindp_ctx *ctx, const char *who, const chaindp_post_opt_t *opt, int64_t n_reads, const int32_t *rep_len, const int32_t *d_rep_len)
+{
+	return align_post_impl(ctx, who, opt, n_reads, rep_len, ctx->rd_need[0], ctx->rd_need[1], nullptr, nullptr, nullptr, nullptr, nullptr, d_rep_len);
+}
+
+int chaindp::align_post_deliver(chaindp_ctx *ctx, const char *who, int64_t n_reads, int64_t *out_off, chaindp_reg_t *out_regs, chaindp_align_extra_t *out_extra,
+                                int32_t *out_dp_max2, int64_t regs_cap, int64_t *cigar_off, uint32_t *cigar, int64_t cigar_cap, int64_t need[2])
+{
+	return deliver(ctx, who, n_reads, out_off, out_regs, out_extra, out_dp_max2, regs_cap, cigar_off, cigar, cigar_cap, need);
 }
 
 extern "C" int chaindp_align_post_fetch(chaindp_ctx_t *ctx, int64_t n_reads, int64_t *out_off, chaindp_reg_t *out_regs, chaindp_align_extra_t *out_extra,

@@ -13,7 +13,7 @@ extern "C" int chaindp_backtrack(chaindp_ctx_t *ctx, const chaindp_params_t *par
 	if (rc) return rc;
 	if (!ctx->ran || !ctx->d_seeds) { ctx->err = "chaindp_backtrack needs a completed run and compaction"; return CHAINDP_ERR_ARG; }
 	if (!chains_off || !b_off) { ctx->err = "NULL output"; return CHAINDP_ERR_ARG; }
-	ctx->regs_resident = false;
+	ctx->regs_resident = false; ctx->post_n_reads = -1;
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	// the record count of the last compaction (it may have been launched asynchronously by chaindp_run_full)
 	unsigned long long n_seeds = 0;
@@ -96,7 +96,7 @@ int chaindp::gen_regs_impl(chaindp_ctx *ctx, const uint32_t *hash, const int32_t
 	const int64_t R = ctx->bot_n_reads, n_c = ctx->bot_n_chains;
 	if (R > 0 && (!hash || !qlen)) { ctx->err = "NULL hash or qlen"; return CHAINDP_ERR_ARG; }
 	if (download && n_c > 0 && !regs) { ctx->err = "NULL output"; return CHAINDP_ERR_ARG; }
-	ctx->regs_resident = false;
+	ctx->regs_resident = false; ctx->post_n_reads = -1;
 	if (R == 0 || n_c == 0) { ctx->regs_resident = true; return CHAINDP_OK; }
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	int rc = regs_per_read_buffers(ctx);
@@ -139,7 +139,7 @@ extern "C" int chaindp_est_err(chaindp_ctx_t *ctx, const int64_t *regs_off, chai
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	if ((rc = regs_per_read_buffers(ctx)) != CHAINDP_OK) return rc;
 	hipStream_t st = ctx->stream;
-	ctx->regs_resident = false;                                  // the upload below replaces what chaindp_gen_regs left in d_regs / d_rqlen
+	ctx->regs_resident = false; ctx->post_n_reads = -1;          // the upload below replaces what chaindp_gen_regs left in d_regs / d_rqlen
 	// every hit's anchors must lie inside its read's chain anchors: checked here, on the host's copy of the offsets
 	{
 		std::vector<int64_t> boff((size_t)R + 1);

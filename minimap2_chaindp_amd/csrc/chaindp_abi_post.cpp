@@ -55,6 +55,7 @@ int chaindp::post_logf_upload(chaindp_ctx *ctx)
 // everything chaindp_chain_post and chaindp_frag_post share on the device, for a batch of n_c chains with n_b chain anchors
 int chaindp::post_reserve(chaindp_ctx *ctx, int64_t n_c, int64_t n_b)
 {
+	ctx->post_n_reads = -1;                              // the caller is about to overwrite what a finished chaindp_chain_post left there
 	int rc = regs_per_read_buffers(ctx);
 	if (rc) return rc;
 	if ((rc = post_logf_upload(ctx)) != CHAINDP_OK) return rc;
@@ -141,11 +142,26 @@ extern "C" int chaindp_chain_post(chaindp_ctx_t *ctx, const chaindp_post_opt_t *
                                   const int32_t *ref_len, int32_t n_ref, const int64_t *mini_pos_off, const uint64_t *mini_pos,
                                   int64_t *regs_off, chaindp_reg_t *regs, int64_t regs_cap, int64_t *a_off, chaindp_anchor_t *a)
 {
+	return chain_post_impl(ctx, opt, qlen, rep_len, ref_len, n_ref, mini_pos_off, mini_pos, regs_off, regs, regs_cap, a_off, a, false);
+}
+
+// A call that runs to its end leaves the batch's final hits whole in HBM (post_out at d_post_off, the anchors in post_sq) and says so in
+// ctx->post_n_reads, for chaindp_align_resident; any other way out leaves it at -1.
+int chaindp::chain_post_impl(chaindp_ctx *ctx, const chaindp_post_opt_t *opt, const int32_t *qlen, const int32_t *rep_len, const int32_t *ref_len, int32_t n_ref,
+                             const int64_t *mini_pos_off, const uint64_t *mini_pos, int64_t *regs_off, chaindp_reg_t *regs, int64_t regs_cap, int64_t *a_off,
+                             chaindp_anchor_t *a, bool keep_only)
+{
 	if (!ctx) return CHAINDP_ERR_ARG;
-	if (!opt || !regs_off || regs_cap < 0 || (regs_cap > 0 && !regs) || n_ref < 0 || (n_ref > 0 && !ref_len) || (a && !a_off)) {
+	if (!opt || !regs_off || (!keep_only && (regs_cap < 0 || (regs_cap > 0 && !regs))) || n_ref < 0 || (n_ref > 0 && !ref_len) || (a && !a_off)) {
 		ctx->err = "NULL argument"; return CHAINDP_ERR_ARG;
 	}
 	if (int rc = post_require_hits(ctx, "chaindp_chain_post")) return rc;
+	ctx->post_n_reads = -1;
+	auto whole = [&](int64_t n_reads, int64_t n_out) {
+		ctx->post_n_out = n_out; ctx->post_cigar = (opt->flag & CHAINDP_F_CIGAR) != 0;
+		ctx->post_ref_len.assign(ref_len, ref_len + n_ref);
+		ctx->post_n_reads = n_reads;
+	};
 	const int64_t R = ctx->bot_n_reads, n_c = ctx->bot_n_chains, n_b = ctx->bot_n_b;
 	const bool do_mapq = !(opt->flag & CHAINDP_F_CIGAR), do_err = !opt->is_sr;
 	hipStream_t st = ctx->stream;
@@ -160,6 +176,7 @@ extern "C" int chaindp_chain_post(chaindp_ctx_t *ctx, const chaindp_post_opt_t *
 	}
 	if (R == 0 || n_c == 0) {
 		for (int64_t r = 0; r <= R; ++r) { regs_off[r] = 0; if (a_off) a_off[r] = 0; }
+		whole(R, 0);
 		return CHAINDP_OK;
 	}
 	int rc = do_err ? mini_pos_check(ctx, mini_pos_off, mini_pos) : CHAINDP_OK;
@@ -179,7 +196,7 @@ extern "C" int chaindp_chain_post(chaindp_ctx_t *ctx, const chaindp_post_opt_t *
 	HIP_TRY(ctx, hipMemcpyAsync(regs_off, ctx->d_post_off, (size_t)(R + 1) * 8, hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipStreamSynchronize(st));
 	const int64_t n_out = regs_off[R];
-	if (n_out > regs_cap) { ctx->err = "more hits than regs has room for (regs_off is valid)"; return CHAINDP_ERR_CAPACITY; }
+	if (!keep_only && n_out > regs_cap) { ctx->err = "more hits than regs has room for (regs_off is valid)"; return CHAINDP_ERR_CAPACITY; }
 	if (do_err && n_out > 0) {
 		const int64_t *d_mpo = nullptr;
 		const unsigned long long *d_mp = nullptr;
@@ -191,10 +208,12 @@ extern "C" int chaindp_chain_post(chaindp_ctx_t *ctx, const chaindp_post_opt_t *
 	if (do_mapq && n_out > 0)
 		HIP_TRY(ctx, chaindp::launch_post_mapq(st, R, ctx->d_post_off, d_rep, opt->min_chain_score, ctx->d_logf_k, ctx->d_logf_v, ctx->n_logf,
 		                                       ctx->post_out.p, ctx->d_post_err));
-	if (n_out > 0) HIP_TRY(ctx, hipMemcpyAsync(regs, ctx->post_out.p, (size_t)n_out * sizeof(chaindp_reg_t), hipMemcpyDeviceToHost, st));
+	if (n_out > 0 && !keep_only) HIP_TRY(ctx, hipMemcpyAsync(regs, ctx->post_out.p, (size_t)n_out * sizeof(chaindp_reg_t), hipMemcpyDeviceToHost, st));
 	if (a_off) HIP_TRY(ctx, hipMemcpyAsync(a_off, ctx->bot.b_off, (size_t)(R + 1) * 8, hipMemcpyDeviceToHost, st));
 	if (a && n_b > 0) HIP_TRY(ctx, hipMemcpyAsync(a, ctx->post_sq.p, (size_t)n_b * 16, hipMemcpyDeviceToHost, st));
-	return post_finish(ctx);
+	if ((rc = post_finish(ctx)) != CHAINDP_OK) return rc;
+	whole(R, n_out);
+	return CHAINDP_OK;
 }
 
 extern "C" int chaindp_map_reads(chaindp_ctx_t *ctx, const chaindp_index_t *ix, int flag, int max_occ, const chaindp_params_t *par, int min_cnt,

@@ -147,7 +147,8 @@ extern "C" int chaindp_align_reads(chaindp_ctx_t *ctx, const chaindp_align_opt_t
 }
 
 int chaindp::align_reads_compute(chaindp_ctx *ctx, const chaindp_align_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seq, const int64_t *a_off,
-                                 chaindp_anchor_t *a, const int64_t *regs_off, const chaindp_reg_t *regs, int64_t regs_cap, int64_t cigar_cap)
+                                 chaindp_anchor_t *a, const int64_t *regs_off, const chaindp_reg_t *regs, int64_t regs_cap, int64_t cigar_cap,
+                                 const AlignResident *from, bool marks_down)
 {
 	const int64_t n_t = (int64_t)ctx->al_t_off.size() - 1;
 	AlignPlan plan0;
@@ -158,31 +159,35 @@ int chaindp::align_reads_compute(chaindp_ctx *ctx, const chaindp_align_opt_t *op
 	if (!ksw_plan_score(o.a, o.b, o.q, o.e, o.q2, o.e2, sc)) { ctx->err = "chaindp_align_reads: scoring"; return CHAINDP_ERR_ARG; }
 	ctx->rd_n_reads = -1;                                // whatever was resident is no longer
 	ctx->rd_need[0] = ctx->rd_need[1] = 0;
+	if (!from) ctx->ho_n_reads = -1;                     // ... nor is it a hand-off's
 	ctx->rd_rounds.clear(); ctx->rd_list_off.clear(); ctx->rd_item.clear();
 	if (n_reads == 0) {
 		ctx->rd_n_reads = 0;
 		return CHAINDP_OK;
 	}
 	const int64_t n_bases = seq_off[n_reads], n_a = a_off[n_reads];
-	if (n_bases > 0 && !seq) { ctx->err = "chaindp_align_reads: NULL sequence"; return CHAINDP_ERR_ARG; }
+	if (n_bases > 0 && !seq && !from) { ctx->err = "chaindp_align_reads: NULL sequence"; return CHAINDP_ERR_ARG; }
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // a buffer that grows is freed: nothing of an earlier call may be in flight
 	hipStream_t st = ctx->stream;
 	int rc;
-	// the reads, once for all rounds
-	Carve in;
-	const size_t o_seq_off = in.take((size_t)(n_reads + 1) * 8), o_a_off = in.take((size_t)(n_reads + 1) * 8), o_a = in.take((size_t)n_a * 16), o_seq = in.take((size_t)n_bases);
-	if ((rc = ksw_grow(ctx, ctx->rd_in, in.at + 16, "the reads", WHO))) return rc;
-	char *d_in = (char*)ctx->rd_in.p;
-	HIP_TRY(ctx, host_copy(d_in + o_seq_off, seq_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-	HIP_TRY(ctx, host_copy(d_in + o_a_off, a_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-	if (n_a) HIP_TRY(ctx, host_copy(d_in + o_a, a, (size_t)n_a * 16, hipMemcpyHostToDevice, st));
-	if (n_bases) HIP_TRY(ctx, host_copy(d_in + o_seq, seq, (size_t)n_bases, hipMemcpyHostToDevice, st));
-
+	// the reads, once for all rounds: up from the host, or where the caller says they are
+	AlignResident res;
+	if (from) {
+		res.seq_off = from->seq_off; res.seq = from->seq; res.a_off = from->a_off; res.a = from->a;
+	} else {
+		Carve in;
+		const size_t o_seq_off = in.take((size_t)(n_reads + 1) * 8), o_a_off = in.take((size_t)(n_reads + 1) * 8), o_a = in.take((size_t)n_a * 16), o_seq = in.take((size_t)n_bases);
+		if ((rc = ksw_grow(ctx, ctx->rd_in, in.at + 16, "the reads", WHO))) return rc;
+		char *d_in = (char*)ctx->rd_in.p;
+		HIP_TRY(ctx, host_copy(d_in + o_seq_off, seq_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
+		HIP_TRY(ctx, host_copy(d_in + o_a_off, a_off, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, st));
+		if (n_a) HIP_TRY(ctx, host_copy(d_in + o_a, a, (size_t)n_a * 16, hipMemcpyHostToDevice, st));
+		if (n_bases) HIP_TRY(ctx, host_copy(d_in + o_seq, seq, (size_t)n_bases, hipMemcpyHostToDevice, st));
+		res.seq_off = (const int64_t*)(d_in + o_seq_off); res.seq = d_in + o_seq; res.a_off = (const int64_t*)(d_in + o_a_off); res.a = d_in + o_a;
+	}
 	ReadsPlan pl;
 	reads_begin(pl, n_reads, regs_off);
-	AlignResident res;
-	res.seq_off = (const int64_t*)(d_in + o_seq_off); res.seq = d_in + o_seq; res.a_off = (const int64_t*)(d_in + o_a_off); res.a = d_in + o_a;
 	// a stage's CIGARs go behind the words the pool holds
 	res.room = [&](int64_t total, uint32_t **out) -> int {
 		const size_t used = (size_t)pl.cig_words * 4;
@@ -216,7 +221,7 @@ int chaindp::align_reads_compute(chaindp_ctx *ctx, const chaindp_align_opt_t *op
 		r_in.swap(r_next);
 	}
 	// the anchors carry every round's marks now
-	if (n_a) HIP_TRY(ctx, host_copy(a, res.a, (size_t)n_a * 16, hipMemcpyDeviceToHost, st));
+	if (n_a && marks_down) HIP_TRY(ctx, host_copy(a, res.a, (size_t)n_a * 16, hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipStreamSynchronize(st));
 	// one inversion call over the lists as the rounds leave them
 	std::vector<int64_t> l_off;

@@ -150,6 +150,7 @@ int chaindp::collect_seeds_impl(chaindp_ctx *ctx, const chaindp_index_t *ix, int
 	if (rep_len && n_reads) HIP_TRY(ctx, hipMemcpyAsync(rep_len, ctx->d_rep_len, (size_t)n_reads * 4, hipMemcpyDeviceToHost, st));
 	HIP_TRY(ctx, hipStreamSynchronize(st));
 	begin_batch(ctx, n_reads, (int64_t)totals[0], true);
+	ctx->from_sketch = resident;
 	ctx->n_mini_pos = (int64_t)totals[1];
 	return CHAINDP_OK;
 }

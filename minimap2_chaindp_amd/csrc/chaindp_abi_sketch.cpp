@@ -38,6 +38,9 @@ static int sketch_reserve(chaindp_ctx *ctx, int64_t n_bases, int64_t n_chunks, i
 		dev_buf(k.slc, nb),
 		dev_buf(k.sseq, nb * 4),
 		dev_buf(k.scnt, nb * 4)};
+	// the bases of the last sketch go with their buffer: nothing may take them for resident from here on, whether or not the new
+	// buffers can be had (chaindp_align_resident reads sk.seq long after the sketch has finished)
+	ctx->sk_valid = false; ctx->from_sketch = false; ctx->post_n_reads = -1;
 	for (const chaindp::DevBuf &b : bufs) ctx->pool.release(b.slot);
 	ctx->sk_cap_bases = ctx->sk_cap_chunks = ctx->sk_cap_seqs = -1;
 	const hipError_t e = (hipError_t)ctx->pool.alloc_group(bufs, 20);

@@ -140,6 +140,20 @@ struct chaindp_ctx {
 	int ap_dp_sc = 0, ap_n_dp = 0;             // the match_sc whose list ap_dp holds (0: none) and its entries
 	int ap_lds_cap = AP_LDS_CAP;               // chaindp_align_post_debug_set_lds_cap (tests): shorter lists stay in LDS
 	double ap_ms[2] = {-1, -1};                // k_apost_read with the scans, the gathers of the last call made while profiling was on
+	// chain_post to the alignment stages, chaindp_align_resident (allocated on first use, grown with the batch): a_off with the scan's
+	// scratch behind it; the squeezed anchors; the regions with their new `as`
+	chaindp::DevGrow ho_off, ho_a, ho_regs, ho_in;   // (ho_in: what chaindp_map_align_debug_run_handoff brings up)
+	int64_t post_n_reads = -1;                 // reads of the batch whose chaindp_chain_post result is whole in post_out / post_sq / d_post_off (-1: none)
+	int64_t post_n_out = 0;                    // its final regions
+	bool post_cigar = false;                   // it ran with MM_F_CIGAR
+	std::vector<int32_t> post_ref_len;         // the ref_len it was given
+	bool from_sketch = false;                  // the resident batch's minimizers were the resident sketch's (begin_batch clears it)
+	int64_t ho_n_reads = -1;                   // reads of the last hand-off (-1: none) and the host's copy of what it left, which the planner reads
+	std::vector<int64_t> ho_h_regs_off, ho_h_a_off;
+	std::vector<int32_t> ho_h_regs;
+	std::vector<uint64_t> ho_h_a;
+	int ho_lds_cap = HO_LDS_CAP;              // chaindp_map_align_debug_set_lds_cap (tests): shorter lists stay in LDS
+	double ho_ms = -1;                         // the hand-off's kernels in the last chaindp_align_resident made while profiling was on
 	int frag_lds_cap = FRAG_LDS_CAP;           // chaindp_debug_set_frag_lds_cap (tests): fewer hits per fragment stay in LDS
 	// sketch (allocated on first use, grown with the batch)
 	chaindp::SketchArgs sk = {};
@@ -271,9 +285,22 @@ int align1_impl(chaindp_ctx *ctx, const chaindp_align_opt_t *opt, int64_t n_read
 int align1_inv_impl(chaindp_ctx *ctx, const chaindp_align_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seq, const int64_t *regs_off,
                     const chaindp_reg_t *regs, int32_t *made, chaindp_reg_t *r_inv, chaindp_align_extra_t *extra, int64_t *cigar_off, uint32_t *cigar,
                     int64_t cigar_cap, AlignResident *res);
-// chaindp_align_reads up to its resident result (chaindp_abi_reads.cpp): everything but the delivery into the caller's arrays
+// chaindp_align_reads up to its resident result (chaindp_abi_reads.cpp): everything but the delivery into the caller's arrays.
+// from == nullptr: the reads go up from the host arrays.  Else the reads are on the device already (from's seq_off, seq, a_off, a;
+// chaindp_align_resident): nothing of them goes up, seq is not read, the host's seq_off, a_off, a and regs serve the planner alone,
+// and a receives the device anchors' marks only with marks_down.
 int align_reads_compute(chaindp_ctx *ctx, const chaindp_align_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seq, const int64_t *a_off,
-                        chaindp_anchor_t *a, const int64_t *regs_off, const chaindp_reg_t *regs, int64_t regs_cap, int64_t cigar_cap);
+                        chaindp_anchor_t *a, const int64_t *regs_off, const chaindp_reg_t *regs, int64_t regs_cap, int64_t cigar_cap,
+                        const AlignResident *from = nullptr, bool marks_down = true);
+// chaindp_chain_post (chaindp_abi_post.cpp); keep_only: the final hits stay in HBM, regs_off is filled, regs and regs_cap are not looked at
+int chain_post_impl(chaindp_ctx *ctx, const chaindp_post_opt_t *opt, const int32_t *qlen, const int32_t *rep_len, const int32_t *ref_len, int32_t n_ref,
+                    const int64_t *mini_pos_off, const uint64_t *mini_pos, int64_t *regs_off, chaindp_reg_t *regs, int64_t regs_cap, int64_t *a_off,
+                    chaindp_anchor_t *a, bool keep_only);
+// the stage of chaindp_align_post over the resident result of align_reads_compute, and the delivery of its own result (chaindp_abi_apost.cpp).
+// d_rep_len: the reads' rep_len on the device (rep_len is then not read), or nullptr: rep_len comes up from the host
+int align_post_resident(chaindp_ctx *ctx, const char *who, const chaindp_post_opt_t *opt, int64_t n_reads, const int32_t *rep_len, const int32_t *d_rep_len);
+int align_post_deliver(chaindp_ctx *ctx, const char *who, int64_t n_reads, int64_t *out_off, chaindp_reg_t *out_regs, chaindp_align_extra_t *out_extra,
+                       int32_t *out_dp_max2, int64_t regs_cap, int64_t *cigar_off, uint32_t *cigar, int64_t cigar_cap, int64_t need[2]);
 int collect_seeds_impl(chaindp_ctx *ctx, const chaindp_index_t *ix, int flag, int max_occ, int64_t n_reads,
                        const int64_t *mini_off, const chaindp_anchor_t *mini, const chaindp_anchor_t *const *read_mini,
                        const uint32_t *bid, const int32_t *qlen,

@@ -8,6 +8,7 @@
 #include "chaindp_align_plan.h"
 #include "chaindp_inv_plan.h"
 #include "chaindp_reads_plan.h"
+#include "chaindp_handoff_plan.h"
 
 namespace chaindp {
 
@@ -440,6 +441,19 @@ hipError_t launch_apost_read(hipStream_t st, const PostOpt &o, const ApostDev &d
 hipError_t launch_apost_gather(hipStream_t st, const ApostDev &d);
 // out[k - 1] = the device's logf((float)k / match_sc) for k in [1, kmax]
 hipError_t launch_apost_logf_probe(hipStream_t st, int kmax, int match_sc, const uint32_t *d_k, const float *d_v, int n, float *d_out);
+
+// From chain_post to the alignment stages (mm_squeeze_a as mm_align_skeleton runs it, align.c:721): handoff/chaindp_handoff.hip.  In: the
+// packed final regions of chaindp_chain_post with their offsets, each read's chain anchors as chain_post left them (sq, at b_off).  Out:
+// a_off[n_reads + 1] (per-read totals, scanned in place; the batch's total at [n_reads]), the squeezed anchors, and the regions with `as`
+// relative to their read's first squeezed anchor.  Room for as many anchors as sq holds.
+struct HandoffDev {
+	int64_t n_reads;
+	const unsigned long long *regs_off; const int32_t *regs; const int64_t *b_off; const void *sq;
+	unsigned long long *a_off; void *a; int32_t *out_regs;
+	int32_t *err;                        // zeroed by the host; set where a region does not lie inside its read's anchors (its anchors are then not moved)
+};
+// d_tile: the scan's scratch, n_reads / 1024 + 2 words.  lds_cap: lists of up to so many regions are ranked in LDS (at most HO_LDS_CAP)
+hipError_t launch_handoff(hipStream_t st, const HandoffDev &d, unsigned long long *d_tile, int lds_cap);
 
 } // namespace chaindp
 #endif
